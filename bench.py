@@ -14,6 +14,13 @@ the MAX-over-ranks time reduction run over gloo on the host, not RCCL.
     python bench.py [--gpus N] [--steps K] [--warmup W]     (spawns N ranks itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
+A plain run does what the headline figure needs and nothing else: generate the
+input on the GPU, warm up, time the K steps, print the line.  --full adds every
+other leg after the timed region (PCIe-inclusive copy, parity against the
+oracle, streaming ingest, per-frame drop-in latency, CPU baselines); without it
+their fields are null.  --dump-outputs DIR writes what the last timed step
+returned (see dump_outputs) so that two builds can be compared array by array.
+
 Rank 0 prints ONE JSON line.  See DESIGN.md "Measurement" for every field.
 """
 from __future__ import annotations
@@ -197,16 +204,26 @@ def parse(argv=None):
                     help="receiver semantics: reference parity (default); dec752 "
                          "(decimated_frame[752]), fft (kiss_fft hunt) or both: SURVEY.md 8f "
                          "rank 3 variants, not reference parity")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the PCIe-inclusive "
+                         "copy, --verify, --stream-chunks, --frame-latency, --cpu-channels and "
+                         "--cpu-all-channels (without --full none of them runs, whatever their "
+                         "options say, and their fields in the line are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs to DIR/<name>.npy "
+                         "(float32/float64, a fixed seeded channel sample of bits; see "
+                         "dump_outputs)")
     ap.add_argument("--cpu-channels", type=int, default=4096,
-                    help="channels of the bounded CPU-baseline sample (0: skip)")
+                    help="--full: channels of the bounded CPU-baseline sample (0: skip)")
     ap.add_argument("--verify", type=int, default=256,
-                    help="channels checked against the oracle after timing (0: skip)")
+                    help="--full: channels checked against the oracle after timing (0: skip)")
     ap.add_argument("--stream-chunks", type=int, default=12,
-                    help="chunks through the streaming-ingest pipeline after timing (0: skip)")
+                    help="--full: chunks through the streaming-ingest pipeline after timing "
+                         "(0: skip)")
     ap.add_argument("--stream-frames", type=int, default=4, help="frames per stream chunk")
     ap.add_argument("--frame-latency", type=int, default=512,
-                    help="frames of one synthetic channel timed through the per-frame drop-in "
-                         "qpsk_rx_frame() (rank 0; 0: skip)")
+                    help="--full: frames of one synthetic channel timed through the per-frame "
+                         "drop-in qpsk_rx_frame() (rank 0; 0: skip)")
     ap.add_argument("--sweep", action="store_true",
                     help="C5: AWGN Eb/N0 sweep (GPU vs the reference C on host cores)")
     ap.add_argument("--sweep-frames", type=int, default=16)
@@ -215,7 +232,7 @@ def parse(argv=None):
                     help="host processes for the all-cores reference baseline and the sweep "
                          "(0: every CPU this job may use, host_cpus())")
     ap.add_argument("--cpu-all-channels", type=int, default=32768,
-                    help="channels of the multi-core reference sample (0: skip)")
+                    help="--full: channels of the multi-core reference sample (0: skip)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher/sharding rehearsal: every rank forms the host group, takes "
                          "its shard and reduces a zero time, rank 0 prints the shards; no GPU use")
@@ -443,6 +460,50 @@ def valu_from_counters(p, t_launch: float):
     return out
 
 
+DUMP_SEED = 20240229              # channel sample of dump_outputs: fixed, not an option
+DUMP_BITS_BYTES = 40_000_000      # float32 bytes of the sampled bits
+DUMP_VALID_BYTES = 16 << 20       # valid is written whole up to this many float32 bytes
+
+
+def dump_channels(nch: int, nf: int) -> np.ndarray:
+    """The channels of an `nch`-channel shard whose bits dump_outputs writes:
+    all of them when they fit DUMP_BITS_BYTES as float32, else a sorted sample
+    drawn without replacement from a generator seeded with DUMP_SEED (the same
+    channels for the same shape, run after run and build after build)."""
+    k = max(1, min(nch, DUMP_BITS_BYTES // (nf * 62 * 4)))
+    if k == nch:
+        return np.arange(nch, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(nch, k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname: str, bits, valid, c0: int = 0, suffix: str = "") -> dict:
+    """Write what the timed path returned in its last step (the device tensors
+    demod_device filled) as .npy files, at most 64 MB in all:
+
+      channels<suffix>.npy  float64 [k]          global ids of the sampled channels
+      bits<suffix>.npy      float32 [k][nf][62]  bits of those channels
+      valid<suffix>.npy     float32 [nch][nf]    valid flags of every channel of the
+                                                 shard ([k][nf], the sampled channels,
+                                                 when the whole exceeds DUMP_VALID_BYTES)
+
+    `suffix` is "" for one rank and "_rank<r>" for rank r of several.  Returns
+    {file name: shape}."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    nch, nf = valid.shape
+    idx = dump_channels(nch, nf)
+    sel = torch.from_numpy(idx).to(bits.device)
+    arrays = {"channels": (idx + c0).astype(np.float64),
+              "bits": bits.index_select(0, sel).cpu().numpy().astype(np.float32)}
+    v = valid if nch * nf * 4 <= DUMP_VALID_BYTES else valid.index_select(0, sel)
+    arrays["valid"] = v.cpu().numpy().astype(np.float32)
+    written = {}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+        written[f"{name}{suffix}.npy"] = list(a.shape)
+    return written
+
+
 def dry_run(args, world: int, rank: int, local: int, strong: bool) -> None:
     """The multi-rank path up to the first GPU call: host group, shard,
     timing reduction, gather of the per-rank records; rank 0 prints one JSON
@@ -479,6 +540,10 @@ def main():
     strong = not args.weak
     if args.dry_run:
         return dry_run(args, world, rank, local, strong)
+    if not args.full:
+        # a plain run: the timed steps (and --dump-outputs) only
+        args.verify = args.cpu_channels = args.cpu_all_channels = 0
+        args.stream_chunks = args.frame_latency = 0
     pool = None
     if rank == 0 and args.cpu_all_channels > 0 and args.cpu_procs > 1:
         import multiprocessing as mp
@@ -509,11 +574,11 @@ def main():
     x = sc.synth_device(args.seed, nch, nf, args.ebn0, c0=c0, device=local)
     torch.cuda.synchronize()
     t_synth = time.perf_counter() - t
-    # PCIe-inclusive reference point (never `value`), rank 0 only: the same
-    # batch copied in from pageable host memory.  Other ranks keep only the
+    # PCIe-inclusive reference point (never `value`; --full), rank 0 only: the
+    # same batch copied in from pageable host memory.  Other ranks keep only the
     # channels they verify.
     x_host, t_h2d = None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         x_host = x.cpu().numpy()
         t = time.perf_counter()
         x2 = torch.from_numpy(x_host).to(x.device)
@@ -586,6 +651,12 @@ def main():
     if valu is None:
         valu = {}
     valu["survey_minimal_form_bound"] = bound
+
+    # the last timed step's outputs, before any other leg runs
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, bits, valid, c0,
+                              f"_rank{rank}" if world > 1 else "")
 
     # parity spot check of the timed outputs on every rank (checker only; not
     # timed): the first k channels of the rank's shard
@@ -708,8 +779,10 @@ def main():
             "roofline": roofline, "valu": valu, "cpu_baseline": cpu,
             "cpu_baseline_all_cores": cpu_all,
             "rank0_region_ms_per_step": round(region_ms / args.steps, 3),
-            "synth_s": round(t_synth, 2), "h2d_s": round(t_h2d, 2),
-            "h2d_incl_msamples_s": round(nch * nf * FRAME / (t_h2d + tmax / args.steps) / 1e6, 1),
+            "full": args.full, "dumped_outputs": dumped,
+            "synth_s": round(t_synth, 2), "h2d_s": round(t_h2d, 2) if args.full else None,
+            "h2d_incl_msamples_s": (round(nch * nf * FRAME / (t_h2d + tmax / args.steps) / 1e6, 1)
+                                    if args.full else None),
             "stream_pcie_note": "rank 0 only, after the timed region",
             "verified_vs_oracle": all(v is not None and v["ok"] for v in per_rank) if args.verify else None,
             "verified_per_rank": per_rank if args.verify else None,

@@ -5,7 +5,7 @@
 set -o pipefail
 one() {  # label, channels, env...
   local lab=$1 nch=$2; shift 2
-  env "$@" timeout -k 10 300 python bench.py --channels $nch \
+  env "$@" timeout -k 10 300 python bench.py --full --channels $nch \
     --cpu-channels 0 --cpu-all-channels 0 --stream-chunks 0 --verify 64 --steps 5 --warmup 2 \
     | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$nch $lab', d['ms_per_step'], round(d['value']), d['roofline']['kernels_us'], d['verified_vs_oracle'])"
 }

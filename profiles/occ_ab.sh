@@ -24,7 +24,7 @@ L=singlecarrier_amd/csrc/build
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 arms=("prod::" "ab1:$L/lib_ab1.so:" "prod_f::QPSK_ABLATE=front" "ab1_f:$L/lib_ab1.so:QPSK_ABLATE=front" "ab2:$L/lib_ab2.so:")
-B="bench.py --cpu-channels 0 --cpu-all-channels 0 --stream-chunks 0 --frame-latency 0 --steps 5 --warmup 2"
+B="bench.py --full --cpu-channels 0 --cpu-all-channels 0 --stream-chunks 0 --frame-latency 0 --steps 5 --warmup 2"
 for r in $(seq 1 $R); do
   for a in "${arms[@]}"; do
     IFS=: read name lib kv <<< "$a"

@@ -4,7 +4,7 @@
 set -o pipefail
 one() {
   local lab=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --cpu-channels 0 --cpu-all-channels 0 --stream-chunks 0 \
+  env "$@" timeout -k 10 300 python bench.py --full --cpu-channels 0 --cpu-all-channels 0 --stream-chunks 0 \
     --verify 64 --steps 5 --warmup 2 \
     | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lab', d['ms_per_step'], round(d['value']), d['roofline']['kernels_us'], d['verified_vs_oracle'])"
 }
