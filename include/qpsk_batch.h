@@ -88,7 +88,9 @@ int qpsk_rx_reset(qpsk_ctx *ctx);
 int qpsk_rx_channels(const qpsk_ctx *ctx);
 /* QPSK_MODE_* of the context. */
 int qpsk_rx_mode(const qpsk_ctx *ctx);
-/* Frames received so far by every channel of the context. */
+/* Frames received so far by every channel of the context.  The count is 64-bit
+ * throughout: every output is right at any frame index, 2^32 and above
+ * included (a snapshot may carry any index, qpsk_rx_state_load). */
 uint64_t qpsk_rx_frames(const qpsk_ctx *ctx);
 
 /* Per-channel state checkpoint / resume.  Between frames the

@@ -2541,6 +2541,10 @@ int qpsk_rx_launch(qpsk_ctx* c, const int16_t* d_in, int F, uint8_t* d_bits, uin
         c->ev_frames[slot] = F;
     }
     const int parity = (int)(c->calls & 1u);
+    // the kernels use the frame index only as g & 1 (mixer sign, state parity)
+    // and g % QK_KS_FRAMES (descrambler word): its residue mod 2 * 1057 is
+    // right for any 64-bit c->frames, and g0 + F stays far below 2^32
+    const unsigned g0 = (unsigned)(c->frames % (uint64_t)(2 * QK_KS_FRAMES));
     Shape sh = pick_shape(c);
     if (c->stall_calls >= 0 && c->launches >= (uint64_t)c->stall_calls) sh.roles &= ~kDebugStall;
 #define QPSK_LAUNCH(GG, FF, MM, DD, WW, QQ, HH)                                                \
@@ -2551,7 +2555,7 @@ int qpsk_rx_launch(qpsk_ctx* c, const int16_t* d_in, int F, uint8_t* d_bits, uin
                        c->d_ks, c->d_win[0], c->d_win[1], c->d_mi[0], c->d_mi[1], c->d_rt[0],  \
                        c->d_rt[1], d_bits, d_valid, d_trace, reinterpret_cast<float2*>(d_soft), \
                        c->d_jobs, c->d_njobs + parity, c->nch, F,                               \
-                       (unsigned)(c->frames & 0xffffffffu), sh.roles,                          \
+                       g0, sh.roles,                                                           \
                        HH ? reinterpret_cast<const float*>(c->d_heads) : c->d_fft,             \
                        (unsigned long long)c->jobs_cap, d_err)
 #define QPSK_LAUNCH_SHAPES(MM, HH)                                                             \
@@ -2569,7 +2573,7 @@ int qpsk_rx_launch(qpsk_ctx* c, const int16_t* d_in, int F, uint8_t* d_bits, uin
         const size_t ncf = (size_t)c->nch * (size_t)F;
         hipLaunchKernelGGL(head_kernel, dim3((unsigned)((ncf + 3) / 4)), dim3(256), 0, s, d_in,
                            c->d_hist, c->d_ptab, c->d_heads, c->nch, F,
-                           (unsigned)(c->frames & 0xffffffffu));
+                           g0);
         HCHECK(hipGetLastError());
         QPSK_LAUNCH_SHAPES(0, true);
     } else
