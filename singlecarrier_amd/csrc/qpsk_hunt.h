@@ -34,15 +34,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <utility>
 
 #include "qpsk_consts.h"
-
-#ifndef QPSK_HUNT_OVERLAP
-// 1: W's wave reduction after the MFMAs are issued (C3 -0.4%, 8,192 channels
-// -0.8%, 16,384 +0.3%: profiles/r05_hov_ab_*.txt); 0: round 4's order (A/B knob)
-#define QPSK_HUNT_OVERLAP 1
-#endif
 
 namespace qhunt {
 
@@ -69,20 +62,6 @@ __device__ __forceinline__ void bconst(int lane, float (&B)[kSteps]) {
         const unsigned long long m = i < 64 ? lo : hi;
         const float v = ((m >> (i & 63)) & 1ull) ? 1.0f : -1.0f;
         B[s] = (i >= 0 && i < QK_NPRE) ? v : 0.0f;
-    }
-}
-
-// The B fragments as a shared LDS table (9 KB per workgroup, written once):
-// BT[t][lane] = B[4t .. 4t+3] of that lane, read back as one 16-B load per 4
-// steps (a kernel with no registers to spare keeps them here).
-constexpr int kBT = kSteps * 64;    // floats
-__device__ __forceinline__ void bconst_lds(int tid, int nthreads, float* BT) {
-    for (int l = tid; l < 64; l += nthreads) {
-        float B[kSteps];
-        bconst(l, B);
-#pragma unroll
-        for (int t = 0; t < kSteps / 4; t++)
-            reinterpret_cast<f4*>(BT)[t * 64 + l] = f4{B[4 * t], B[4 * t + 1], B[4 * t + 2], B[4 * t + 3]};
     }
 }
 
@@ -130,101 +109,9 @@ __device__ __forceinline__ f4 correlate(int lane, const float* TK, const float (
     return acc;
 }
 
-// Same chain with B from the LDS table of bconst_lds().
-__device__ __forceinline__ f4 correlate_bt(int lane, const float* TK, const float* BT) {
-    const int m = lane & 15, kk = lane >> 4;
-    const int a = m >> 1, comp = m & 1;
-    const f4* src = reinterpret_cast<const f4*>(TK + (kk * 2 + comp) * kRow + 4 * a);
-    const f4* bsrc = reinterpret_cast<const f4*>(BT) + lane;
-    f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int t = 0; t < kSteps / 4; t++) {
-        const f4 v = src[t];
-        const f4 b = bsrc[64 * t];
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(v.x, b.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(v.y, b.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(v.z, b.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(v.w, b.w, acc, 0, 0, 0);
-    }
-    return acc;
-}
-
 // lags held by this lane's fragment: (re, im) = (acc[0], acc[1]) and (acc[2], acc[3])
 __device__ __forceinline__ int lag_lo(int lane) { return 32 * (lane >> 4) + (lane & 15); }
 __device__ __forceinline__ int lag_hi(int lane) { return lag_lo(lane) + 16; }
-
-// ------------------------------------------------------------ VALU form
-// The same k-ordered chains on the vector ALU.  An f32 MFMA occupies its
-// SIMD's VALU for its whole issue time: beside a dependent
-// v_mfma_f32_16x16x4_f32 chain another wave's v_pk_add_f32 stream slows from
-// 5.0 to 13.0 cycles per instruction (profiles/calib/mfma_mix_r02.txt), so
-// the 36 MFMAs per channel (~1,150 SIMD cycles) cost every wave on the SIMD.
-// Here lane l owns lags 2l and 2l+1; step k adds p_k * T[2l+k] and
-// p_k * T[2l+1+k] with one v_pk_add_f32 each ((re, im) packed; p_k = -1 is a
-// negation modifier: RN(acc - T) == fmaf(-1, T, acc)).  One 16-B LDS read of
-// (T[2l+k], T[2l+k+1]) (k even) serves both lags for two steps: 65 reads and
-// 256 packed adds per channel.
-constexpr int kTV = 256;            // float2 per T image (2 KB)
-
-// TV[j] = T[j] = (RN(dr - di), RN(di + dr)) for j < 255, TV[255] = 0.
-// Lane l handles j = l + 64r: 8-B reads and writes at 8-B lane stride.
-__device__ __forceinline__ void store_tv(int lane, const float2* dec, float2* TV) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int j = lane + 64 * r;
-        float tr = 0.0f, ti = 0.0f;
-        if (j < 2 * QK_NLAG - 1) {
-            const float2 d = dec[j];
-            tr = d.x - d.y;
-            ti = d.y + d.x;
-        }
-        TV[j] = make_float2(tr, ti);
-    }
-}
-
-typedef float v2 __attribute__((ext_vector_type(2)));
-
-template <bool NEG>
-__device__ __forceinline__ v2 acc_add(v2 a, v2 t) {
-    v2 r;
-    if (NEG) asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(t));
-    else asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(t));
-    return r;
-}
-
-template <int K>
-__device__ __forceinline__ v2 acc_step(v2 a, v2 t) {
-    constexpr unsigned long long m = K < 64 ? pre_mask(0) : pre_mask(1);
-    return acc_add<((m >> (K & 63)) & 1ull) == 0>(a, t);
-}
-
-template <int... I>
-__device__ __forceinline__ void chain_valu(const f4* src, v2& a0, v2& a1,
-                                           std::integer_sequence<int, I...>) {
-    // step pair (2i, 2i+1): q = (T[2l+2i], T[2l+2i+1]), n = (T[2l+2i+2], ..)
-    f4 q = src[0];
-    auto pair = [&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        const f4 n = src[i + 1];
-        a0 = acc_step<2 * i>(a0, v2{q.x, q.y});
-        a1 = acc_step<2 * i>(a1, v2{q.z, q.w});
-        a0 = acc_step<2 * i + 1>(a0, v2{q.z, q.w});
-        a1 = acc_step<2 * i + 1>(a1, v2{n.x, n.y});
-        q = n;
-    };
-    (pair(std::integral_constant<int, I>{}), ...);
-}
-
-// Returns (re, im) of lag 2l in [0], [1] and of lag 2l+1 in [2], [3].
-__device__ __forceinline__ f4 correlate_valu(int lane, const float2* TV) {
-    const f4* src = reinterpret_cast<const f4*>(TV + 2 * lane);
-    v2 a0 = {0.0f, 0.0f}, a1 = {0.0f, 0.0f};
-    chain_valu(src, a0, a1, std::make_integer_sequence<int, QK_NPRE / 2>{});
-    return f4{a0.x, a0.y, a1.x, a1.y};
-}
-
-__device__ __forceinline__ int lag_lo_valu(int lane) { return 2 * lane; }
-__device__ __forceinline__ int lag_hi_valu(int lane) { return 2 * lane + 1; }
 
 // ------------------------------------------------------- filtered hunt
 // The hunt needs only max_index (src/qpsk.c:172-183; max_value reaches no
@@ -455,22 +342,16 @@ __device__ __forceinline__ int hunt_index(int lane, const float2* dec, float* S,
     char* H = reinterpret_cast<char*>(S);
     const float w = store_h(lane, dec, H);
     fb = false;
-#if QPSK_HUNT_OVERLAP
     // the MFMAs first, W's DPP reduction in their shadow (neither waits for
-    // the other; the all-zero test only needs W before the pick)
+    // the other; C3 -0.4%, 8,192 channels -0.8%, 16,384 +0.3% against reducing
+    // first: profiles/r05_hov_ab_*.txt).  An all-zero window (W sums
+    // non-negative terms: 0 only if every T is): every sum is 0, so no lag
+    // exceeds the initial max and max_index stays 0
     lds_sync();
     const f4 acc = correlate_h(lane, H, TB);
     const float W = wave_sum_f32(w);
     if (W == 0.0f) return 0;
     const int pick = pick_h(lane, acc, W, wave_max);
-#else
-    const float W = wave_sum_f32(w);
-    // an all-zero window (W sums non-negative terms: 0 only if every T is):
-    // every sum is 0, so no lag exceeds the initial max and max_index stays 0
-    if (W == 0.0f) return 0;
-    lds_sync();
-    const int pick = pick_h(lane, correlate_h(lane, H, TB), W, wave_max);
-#endif
     fb = pick < 0;
     if (!fb) return pick;
     lds_sync();   // the exact image overwrites H

@@ -42,6 +42,17 @@
 
 #pragma clang fp contract(off)
 
+// Compile-time A/B knobs whose rejected branches are gone: a -D of one of them
+// would build this source unchanged and compare it with itself.
+#if defined(QPSK_FRESH) || defined(QPSK_FRESH_SPLIT) || defined(QPSK_HUNT_MFMA) || \
+    defined(QPSK_HUNT_FILTER) || defined(QPSK_HUNT_OVERLAP) || defined(QPSK_FIR_WAIT) || \
+    defined(QPSK_FIR_ANCHOR) || defined(QPSK_FIR_SPLIT) || defined(QPSK_SPLIT_BANKS) || \
+    defined(QPSK_QDMUL) || defined(QPSK_TRAIN_PRETAB) || defined(QPSK_DYNPRIO) || \
+    defined(QPSK_DATA_RING) || defined(QPSK_LATE_YIELD) || defined(QPSK_FB) || defined(QPSK_FB1) || \
+    defined(QPSK_ZERO_COPY)
+#error "QPSK_FRESH, QPSK_FRESH_SPLIT, QPSK_HUNT_MFMA, QPSK_HUNT_FILTER, QPSK_HUNT_OVERLAP, QPSK_FIR_WAIT, QPSK_FIR_ANCHOR, QPSK_FIR_SPLIT, QPSK_SPLIT_BANKS, QPSK_QDMUL, QPSK_TRAIN_PRETAB, QPSK_DYNPRIO, QPSK_DATA_RING, QPSK_LATE_YIELD, QPSK_FB, QPSK_FB1 and QPSK_ZERO_COPY were removed with their alternative branches: DESIGN.md, Removed knobs, names the commit that still has each"
+#endif
+
 namespace {
 
 // A workgroup owns G groups of 64 channels: waves 0..G-1 are their back waves,
@@ -64,70 +75,16 @@ constexpr int kDec = 296;
 // TU (255 correlator terms, permuted) reuses M once the FIR is done.  MODE 1
 // keeps one dec buffer per front wave (LDS budget); the previous channel's
 // window is read from it before the FIR overwrites it (same wave, in order).
-#ifndef QPSK_FB
-#define QPSK_FB 15   // FIR samples per LDS batch (A/B knob)
-#endif
 #ifndef QPSK_RX_ATTR
 #define QPSK_RX_ATTR   // A/B: e.g. __attribute__((amdgpu_num_vgpr(128))) to price a 4-wave budget
 #endif
-#ifndef QPSK_FRESH
-#define QPSK_FRESH 0   // 1: recompute the prefetch/mixer per-lane constants at each use (register A/B knob)
-#endif
-#ifndef QPSK_HUNT_MFMA
-#define QPSK_HUNT_MFMA 1   // 1: hunt on the matrix cores; 0: packed VALU chains (A/B knob)
-#endif
-#ifndef QPSK_HUNT_FILTER
-#define QPSK_HUNT_FILTER 1   // 1: bf16 first pass, exact chain only when the argmax is in doubt (qpsk_hunt.h)
-#endif
-#ifndef QPSK_FIR_WAIT
-#define QPSK_FIR_WAIT 1   // the FIRs: one lgkmcnt(0) per sample batch, not one per sample (0: A/B knob)
-#endif
-#ifndef QPSK_LATE_YIELD
+constexpr int kFirBatch = 15;   // FIR samples per LDS batch (fir_dec, fir_dec752, fir_split)
 // 4x2 fronts: the frame's last K channels at the back wave's issue priority.
 // Since the anchored FIR the back is the frame's last wave (4.4% of a frame
 // alone, profiles/r06_c19_stamps_c3_both.json); K = 2: C3 -0.7% over 12
 // interleaved rounds (10 faster), K = 1 / 4 +-0, K = 8 +2.4%
-// (profiles/r06_ly_ab.txt, r06_ly2_ab.txt); 0: off
-#define QPSK_LATE_YIELD 2
-#endif
-#ifndef QPSK_FIR_ANCHOR
-// the batched FIRs' accumulators pinned per LDS batch (anchor_f2).  Without it
-// LLVM sinks every multiply-add below the batch's last wait (the FIR ran as
-// rounds of loads, all the arithmetic after them, 59 samples live).  1: the
-// split FIR (the 4x2 kernel: 0 VGPR spills instead of 5, C3 -1.2% over 5
-// interleaved rounds, profiles/r06_anc_ab.txt); 2: every FIR (the dual shapes:
-// +-0 at 8,192-32,768 channels, +1% at 4,096: not kept); 0: round 5's code
-#define QPSK_FIR_ANCHOR 1
-#endif
-#ifndef QPSK_FRESH_SPLIT
-#define QPSK_FRESH_SPLIT 1   // QPSK_FRESH of the 4x2 kernel's fronts with the split FIR (A/B knob)
-#endif
-#ifndef QPSK_FIR_SPLIT
-// the 4x2 kernel in reference mode (MODE 0, not the head pre-pass, not the
-// FFT hunt): before the hunt only dec[0..254], the entries it correlates, in
-// two passes on all 64 lanes (392 packed operations instead of 490);
-// dec[255..289] after it, only when the window's observable part reaches them
-// (fir_split below).  The dual-chain shapes keep fir_dec + fir_head_at: their
-// fronts are latency-bound and the split's extra LDS reads cost them ~1%
-// (profiles/r05_split_ab.txt); 0: A/B knob; 2: every MODE-0 shape (A/B knob)
-#define QPSK_FIR_SPLIT 1
-#endif
-#ifndef QPSK_QDMUL
-#define QPSK_QDMUL 1   // quad step: rotated h times its column mask as v_mul_f32_dpp (qd_mul); 0: A/B knob
-#endif
-#ifndef QPSK_TRAIN_PRETAB
-// 1: the lane back's preamble signs as one scalar load per step from kPreTab
-// instead of ~6 scalar instructions of bit extraction (967 -> 943 instructions
-// per 4 steps; C3 -0.3%, profiles/r05_pretab_data_ab.txt); 0: A/B knob
-#define QPSK_TRAIN_PRETAB 1
-#endif
-#ifndef QPSK_DYNPRIO
-// dynamic issue priority of the dual-chain back waves (rx_kernel): they train
-// at the highest priority unless another back wave waits for its fronts.
-// 1: quad-back shapes (-1.5% at 8,192 channels, -4% at 4,096; lane backs +1..4%:
-// profiles/r03_dynprio_ab.txt); 0: off; 2: every dual-chain shape (A/B knob)
-#define QPSK_DYNPRIO 1
-#endif
+// (profiles/r06_ly_ab.txt, r06_ly2_ab.txt)
+constexpr int kLateYield = 2;
 
 constexpr int kM1 = 1240;
 template <int MODE> struct Cfg;
@@ -329,7 +286,7 @@ __device__ __forceinline__ int fresh_lane(int lane) {
     return lane;
 }
 
-template <int MODE, bool CG = false, int FR = QPSK_FRESH>
+template <int MODE, bool CG = false, int FR = 0>
 __device__ __forceinline__ void prefetch(const Src& s, int lane, int (&r)[kPf<MODE>]) {
     prefetch_seq<MODE, CG>(s, (FR & 1) ? fresh_lane(lane) : lane, r, std::make_integer_sequence<int, kPf<MODE>>{});
 }
@@ -365,7 +322,7 @@ __device__ __forceinline__ void mix_seq(int lane, const int (&r)[kPf<MODE>], con
     (mix_item<MODE, I, NO>(lane, r[I], P, M), ...);
 }
 
-template <int MODE, int FR = QPSK_FRESH>
+template <int MODE, int FR = 0>
 __device__ __forceinline__ void mix(int lane, const int (&r)[kPf<MODE>], unsigned g,
                                     const float2* P, float2* M) {
     constexpr auto kSeq = std::make_integer_sequence<int, kPf<MODE>>{};
@@ -382,9 +339,21 @@ typedef __attribute__((address_space(3))) const volatile f2 lds_vf2;
 __device__ __forceinline__ f2 ld2nt(const float2* p) {
     return *(lds_vf2*)p;   // p points into LDS
 }
-// an accumulator pinned in a VGPR at this point of the instruction stream
-// (QPSK_FIR_ANCHOR: keeps a batch's arithmetic inside it)
+// an accumulator pinned in a VGPR at this point of the instruction stream:
+// keeps a batch's arithmetic inside it.  Without it LLVM sinks every
+// multiply-add below the batch's last wait (the FIR ran as rounds of loads, all
+// the arithmetic after them, 59 samples live).  The split FIR is anchored (the
+// 4x2 kernel: 0 VGPR spills instead of 5, C3 -1.2% over 5 interleaved rounds,
+// profiles/r06_anc_ab.txt); the dual shapes' FIRs are not (+-0 at 8,192-32,768
+// channels, +1% at 4,096)
 __device__ __forceinline__ void anchor_f2(f2& y) { asm volatile("" : "+v"(y)); }
+// one lgkmcnt(0) per LDS sample batch of a FIR, not one per sample
+// (profiles/r04_firwait_ab.txt)
+__device__ __forceinline__ void fir_batch_wait() {
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
+    __builtin_amdgcn_sched_barrier(0);
+}
 
 #ifdef QPSK_STAMPS
 #define FSTAMP(i) do { const unsigned long long t_ = stamp_now(); facc[8 + (i)] += t_ - ft0; ft0 = t_; } while (0)
@@ -407,28 +376,20 @@ __device__ __forceinline__ void fir_dec752(int lane, int rt, const float2* M, fl
         const float2* b = M + 25 * lane + rt;
         f2 y[5] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};
 #pragma unroll
-        for (int s0 = 0; s0 < 69; s0 += QPSK_FB) {
-            f2 v[QPSK_FB];
+        for (int s0 = 0; s0 < 69; s0 += kFirBatch) {
+            f2 v[kFirBatch];
 #pragma unroll
-            for (int j = 0; j < QPSK_FB; j++)
+            for (int j = 0; j < kFirBatch; j++)
                 if (s0 + j < 69) v[j] = ld2nt(b + s0 + j);
-            if (QPSK_FIR_WAIT) {
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            fir_batch_wait();
 #pragma unroll
-            for (int j = 0; j < QPSK_FB; j++) {
+            for (int j = 0; j < kFirBatch; j++) {
                 const int s = s0 + j;
 #pragma unroll
                 for (int m = 0; m < 5; m++) {
                     const int k = s - 5 * m;
                     if (s < 69 && k >= 0 && k < QK_NTAPS) y[m] = y[m] + v[j] * QK_RRC[k];
                 }
-            }
-            if (QPSK_FIR_ANCHOR == 2) {
-#pragma unroll
-                for (int m = 0; m < 5; m++) anchor_f2(y[m]);
             }
         }
 #pragma unroll
@@ -447,9 +408,8 @@ __device__ __forceinline__ void fir_dec752(int lane, int rt, const float2* M, fl
 // inverse [256, 512), Q [512, 768) as (re, im) pairs, then kf_work's input
 // permutation as 256 ints.
 constexpr int kFftHT = 768 * 2 + 256;   // floats
-// hunt tables (floats): the bf16 pass's B table + the exact chain's p line, or
-// the exact chain's B table
-constexpr int kHuntTab = QPSK_HUNT_FILTER ? qhunt::kBH + qhunt::kPL : qhunt::kBT;
+// hunt tables (floats): the bf16 pass's B table + the exact chain's p line
+constexpr int kHuntTab = qhunt::kBH + qhunt::kPL;
 __device__ __forceinline__ int fft_hunt(int lane, float2* M, const float2* dec, const float* HT) {
     const qfft::cf* tw = reinterpret_cast<const qfft::cf*>(HT);
     const int* perm = reinterpret_cast<const int*>(HT + 768 * 2);
@@ -480,7 +440,7 @@ __device__ __forceinline__ int fft_hunt(int lane, float2* M, const float2* dec, 
 // RRC (src/fir.c:36-42), outputs accumulated in tap order.  Decimated outputs
 // D[o] = fir_out[5o + rt] (model A): lane l makes o = 3l..3l+2
 // from the 59 samples M[15l + rt + s], read in batches of FB samples.
-template <int FB = QPSK_FB>
+template <int FB = kFirBatch>
 __device__ __forceinline__ void fir_dec(int lane, int rt, const float2* M, float2* dec) {
     if (lane < 63) {
         const float2* b = M + 15 * lane + rt;
@@ -491,11 +451,7 @@ __device__ __forceinline__ void fir_dec(int lane, int rt, const float2* M, float
 #pragma unroll
             for (int j = 0; j < FB; j++)
                 if (s0 + j < 59) v[j] = ld2nt(b + s0 + j);
-            if (QPSK_FIR_WAIT) {   // one wait per batch instead of one per sample
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            fir_batch_wait();
 #pragma unroll
             for (int j = 0; j < FB; j++) {
                 const int s = s0 + j;
@@ -504,10 +460,6 @@ __device__ __forceinline__ void fir_dec(int lane, int rt, const float2* M, float
                     const int k = s - 5 * m;
                     if (s < 59 && k >= 0 && k < QK_NTAPS) y[m] = y[m] + v[j] * QK_RRC[k];
                 }
-            }
-            if (QPSK_FIR_ANCHOR == 2) {
-#pragma unroll
-                for (int m = 0; m < 3; m++) anchor_f2(y[m]);
             }
         }
 #pragma unroll
@@ -521,31 +473,25 @@ __device__ __forceinline__ void fir_dec(int lane, int rt, const float2* M, float
 
 // One FIR output per lane: out = GAIN * sum_k b[k] * RRC[k], k ascending
 // (the same operations in the same order as fir_dec / fir_head_at).
-#ifndef QPSK_FB1
-#define QPSK_FB1 8   // fir_one's samples per LDS batch (A/B knob)
-#endif
+constexpr int kFirOneBatch = 8;   // fir_one's samples per LDS batch
 __device__ __forceinline__ f2 fir_one(const float2* b) {
     f2 y = {0.0f, 0.0f};
 #pragma unroll
-    for (int s0 = 0; s0 < QK_NTAPS; s0 += QPSK_FB1) {
-        f2 v[QPSK_FB1];
+    for (int s0 = 0; s0 < QK_NTAPS; s0 += kFirOneBatch) {
+        f2 v[kFirOneBatch];
 #pragma unroll
-        for (int j = 0; j < QPSK_FB1; j++)
+        for (int j = 0; j < kFirOneBatch; j++)
             if (s0 + j < QK_NTAPS) v[j] = ld2nt(b + s0 + j);
-        if (QPSK_FIR_WAIT) {
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        fir_batch_wait();
 #pragma unroll
-        for (int j = 0; j < QPSK_FB1; j++)
+        for (int j = 0; j < kFirOneBatch; j++)
             if (s0 + j < QK_NTAPS) y = y + v[j] * QK_RRC[s0 + j];
-        if (QPSK_FIR_ANCHOR >= 1) anchor_f2(y);
+        anchor_f2(y);
     }
     return y * QK_GAIN;
 }
 
-// The split FIR of reference mode (QPSK_FIR_SPLIT).  dec = [D_n[0..187],
+// The split FIR of the 4x2 kernel in reference mode.  dec = [D_n[0..187],
 // F_{n+1}[0..101]]; the hunt correlates dec[0..254] (lags < 128 over 128
 // symbols) and the window's observable entries are dec[mi .. mi+162]
 // (slots past the data symbols never reach an output), so
@@ -574,42 +520,28 @@ constexpr int kSplitMi = 255 - (QK_NPRE + QK_NDSYM + 3);   // 93: mi + 162 >= 25
 // with j = 32, 33 -- profiles/probe/fir_split_banks.py).
 // The map is qpsk_split.h (split_r, split_j1, make_split_tab), checked on the
 // host for every rt by tests/test_split_tab.py.
-// QPSK_SPLIT_BANKS 0: the round-5 mapping (A/B knob).
-#ifndef QPSK_SPLIT_BANKS
-#define QPSK_SPLIT_BANKS 1
-#endif
 static_assert(kSplitM1 == kM1, "qpsk_split.h: F_{n+1}'s offset in M");
 __constant__ SplitTab kSplitTab = make_split_tab();
-constexpr int kSplitTabWords = QPSK_SPLIT_BANKS ? (int)sizeof(SplitTab) / 4 : 1;
+constexpr int kSplitTabWords = (int)sizeof(SplitTab) / 4;
 
 __device__ __forceinline__ void fir_split(int lane, int rt, const float2* M, float2* dec,
                                           const uint8_t* p2tab) {
     lane = fresh_lane(lane);   // the per-lane bases below are recomputed, not kept live across the loop
-#if QPSK_SPLIT_BANKS
     const int r = split_r(__builtin_amdgcn_readfirstlane(rt));
     const int j1 = split_j1(r);
     const int j2 = p2tab[r * 64 + lane];
-#else
-    (void)p2tab;
-    constexpr int j1 = 56;
-    const int j2 = lane + (lane >= 56 ? 1 : 0) + (lane >= 60 ? 1 : 0);
-#endif
     {   // pass 1
         const float2* b = lane < 63 ? M + 15 * lane + rt : M + kM1 + j1;
         f2 y[3] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};
 #pragma unroll
-        for (int s0 = 0; s0 < 59; s0 += QPSK_FB) {
-            f2 v[QPSK_FB];
+        for (int s0 = 0; s0 < 59; s0 += kFirBatch) {
+            f2 v[kFirBatch];
 #pragma unroll
-            for (int j = 0; j < QPSK_FB; j++)
+            for (int j = 0; j < kFirBatch; j++)
                 if (s0 + j < 59) v[j] = ld2nt(b + s0 + j);
-            if (QPSK_FIR_WAIT) {
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            fir_batch_wait();
 #pragma unroll
-            for (int j = 0; j < QPSK_FB; j++) {
+            for (int j = 0; j < kFirBatch; j++) {
                 const int s = s0 + j;
 #pragma unroll
                 for (int m = 0; m < 3; m++) {
@@ -617,10 +549,8 @@ __device__ __forceinline__ void fir_split(int lane, int rt, const float2* M, flo
                     if (s < 59 && k >= 0 && k < QK_NTAPS) y[m] = y[m] + v[j] * QK_RRC[k];
                 }
             }
-            if (QPSK_FIR_ANCHOR >= 1) {
 #pragma unroll
-                for (int m = 0; m < 3; m++) anchor_f2(y[m]);
-            }
+            for (int m = 0; m < 3; m++) anchor_f2(y[m]);
         }
 #pragma unroll
         for (int m = 0; m < 3; m++) {
@@ -660,11 +590,7 @@ __device__ __forceinline__ void fir_head_at(int lane, const float2* H, float2* o
                 v[j] = f2{q.x, q.y};
                 v[j + 1] = f2{q.z, q.w};
             }
-            if (QPSK_FIR_WAIT) {
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            fir_batch_wait();
 #pragma unroll
             for (int j = 0; j < 10; j++) {
                 const int s = s0 + j;
@@ -673,10 +599,6 @@ __device__ __forceinline__ void fir_head_at(int lane, const float2* H, float2* o
                     const int k = s - m;
                     if (k >= 0 && k < QK_NTAPS) y[m] = y[m] + v[j] * QK_RRC[k];
                 }
-            }
-            if (QPSK_FIR_ANCHOR == 2) {
-#pragma unroll
-                for (int m = 0; m < 2; m++) anchor_f2(y[m]);
             }
         }
         const f2 o0 = y[0] * QK_GAIN, o1 = y[1] * QK_GAIN;   // one 16-B store
@@ -734,7 +656,6 @@ __device__ __forceinline__ int hunt(int lane, float2* M, const float2* dec, cons
     unsigned long long ft0 = stamp_now();
 #endif
     if constexpr ((MODE & 2) != 0) return fft_hunt(lane, M, dec, BT);
-#if QPSK_HUNT_MFMA && QPSK_HUNT_FILTER
     // bf16 pass, exact chain when in doubt (qpsk_hunt.h hunt_index)
     bool fb;
     const int mi = qhunt::hunt_index(lane, dec, reinterpret_cast<float*>(M), BT, wave_max_u32, fb);
@@ -744,27 +665,6 @@ __device__ __forceinline__ int hunt(int lane, float2* M, const float2* dec, cons
 #endif
     FSTAMP(2);
     return mi;
-#else
-#if QPSK_HUNT_MFMA
-    // exact chain only (qpsk_hunt.h: bit-identical k-ordered chain)
-    float* TK = reinterpret_cast<float*>(M);
-    qhunt::store_t(lane, dec, TK);
-    wave_lds_sync();
-    FSTAMP(2);
-    const qhunt::f4 acc = qhunt::correlate_bt(lane, TK, BT);
-    FSTAMP(3);
-    return qhunt::argmax_exact(acc, wave_max_u32, qhunt::lag_lo, qhunt::lag_hi);
-#else
-    // as packed VALU chains (qpsk_hunt.h correlate_valu: the same k-ordered sums)
-    float2* TV = M;
-    qhunt::store_tv(lane, dec, TV);
-    wave_lds_sync();
-    FSTAMP(2);
-    const qhunt::f4 acc = qhunt::correlate_valu(lane, TV);
-    FSTAMP(3);
-    return qhunt::argmax_exact(acc, wave_max_u32, qhunt::lag_lo_valu, qhunt::lag_hi_valu);
-#endif
-#endif
 }
 
 // One channel of frame n's front: D_n (decimated with rx_timing rt), F_{n+1},
@@ -1099,12 +999,7 @@ __device__ __forceinline__ int train(Kal& k, f2 (&x)[5], const f2* wp2, bool& ba
     for (int i = 0; i < QK_NPRE; i++) {
         if ((i & 3) == 0) poll();                  // every 4 steps (dynamic priority)
         const f2 nx = wp2[i + 6];                  // slot i+6 (next step)
-#if QPSK_TRAIN_PRETAB
         const float ref = kPreTab.v[i];            // wave-uniform scalar load (kPreTab)
-#else
-        const unsigned long long m = i < 64 ? kPreLo : kPreHi;
-        const float ref = ((m >> (i & 63)) & 1ull) ? 1.0f : -1.0f;
-#endif
         f2 v = {0.0f, 0.0f};
 #pragma unroll
         for (int t = 0; t < 5; t++) v = v + cmul(x[t], k.eq[t]);
@@ -1215,7 +1110,7 @@ __device__ __forceinline__ f2 qd2(f2 v) { return f2{qdf<CTRL>(v.x), qdf<CTRL>(v.
 template <int CTRL>
 __device__ __forceinline__ f2 qd_mul(f2 v, float m) {
     float x = qdf<CTRL>(v.x) * m, y = qdf<CTRL>(v.y) * m;
-    if (QPSK_QDMUL) asm("" : "+v"(x), "+v"(y));
+    asm("" : "+v"(x), "+v"(y));
     return f2{x, y};
 }
 
@@ -1494,9 +1389,7 @@ struct JobX {
     }
 };
 
-#ifndef QPSK_DATA_RING
-#define QPSK_DATA_RING 4   // job samples loaded this many steps ahead (1: one step; profiles/r02_data_ring_ab.txt)
-#endif
+constexpr int kDataRing = 4;   // job samples loaded this many steps ahead (profiles/r02_data_ring_ab.txt)
 template <bool EXACT>
 __device__ __forceinline__ void data_step(Kal& k, f2 (&x)[5], f2 nx, int s, unsigned long long& dib,
                                           float2* so, unsigned& bmax) {
@@ -1518,10 +1411,9 @@ __device__ __forceinline__ unsigned long long data_steps(Kal& k, f2 (&x)[5], con
                                                          float2* so, bool& bad) {
     unsigned long long dib = 0;
     unsigned bmax = 0u;
-#if QPSK_DATA_RING > 1
     // the job's samples arrive from HBM (written ~ms earlier by rx_kernel):
     // each is loaded R steps before it enters x
-    constexpr int R = QPSK_DATA_RING;
+    constexpr int R = kDataRing;
     f2 cur[R];
 #pragma unroll
     for (int t = 0; t < R; t++) cur[t] = xs[min(5 + t, 34)];
@@ -1535,9 +1427,6 @@ __device__ __forceinline__ unsigned long long data_steps(Kal& k, f2 (&x)[5], con
 #pragma unroll
         for (int t = 0; t < R; t++) cur[t] = nxt[t];
     }
-#else
-    for (int s = 0; s < QK_NDSYM; s++) data_step<EXACT>(k, x, xs[min(s + 5, 34)], s, dib, so, bmax);
-#endif
     if (!EXACT) bad |= bmax > __float_as_uint(0x1p125f);
     return dib;
 }
@@ -1611,18 +1500,20 @@ __global__ void __launch_bounds__(256) rx_data_kernel(const float4* jobs, unsign
 //
 // QUAD (DUAL, G == 1 only): the back waves hold a quad of lanes per channel
 // (back_frame_quad), 16 channels per wave, W / 16 waves per frame chain.
-template <int G, int FP, int MODE, bool DUAL, int W, bool QUAD>
+template <int G, bool DUAL, int W, bool QUAD>
 constexpr int kBackWavesOf = DUAL ? 2 * G * (QUAD ? W / 16 : 1) : G;
 
+// An instantiation's waves: rx_kernel's __launch_bounds__ and kBlock and the
+// host's launch (launch_rx) all take the block size from here.
 // waves per SIMD = ceil(waves / 4): 3 (<= 168 VGPRs) for the 12-wave shapes
-template <int G, int FP, int MODE, bool DUAL, int W, bool QUAD>
-constexpr int kWavesOf = kBackWavesOf<G, FP, MODE, DUAL, W, QUAD> + G * FP;
+template <int G, int FP, bool DUAL, int W, bool QUAD>
+constexpr int kWavesOf = kBackWavesOf<G, DUAL, W, QUAD> + G * FP;
 
 //
 // HP: the fronts take F_{n+1} from the head pre-pass (head_kernel, QPSK_HEADPASS).
 template <int G, int FP, int MODE, bool DUAL, int W = QK_GROUP, bool QUAD = false, bool HP = false>
-__global__ void __launch_bounds__((64 * kWavesOf<G, FP, MODE, DUAL, W, QUAD>),
-                                  ((kWavesOf<G, FP, MODE, DUAL, W, QUAD> + 3) / 4)) QPSK_RX_ATTR rx_kernel(
+__global__ void __launch_bounds__((64 * kWavesOf<G, FP, DUAL, W, QUAD>),
+                                  ((kWavesOf<G, FP, DUAL, W, QUAD> + 3) / 4)) QPSK_RX_ATTR rx_kernel(
     const int16_t* in, int16_t* hist, const float2* ptab, const unsigned long long* ks,
     float2* win0, float2* win1, int* mi0, int* mi1, int* rt0, int* rt1, uint8_t* bits,
     uint8_t* valid, int32_t* trace, float2* soft, float4* jobs, unsigned* njobs, int nch, int F,
@@ -1630,12 +1521,16 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, MODE, DUAL, W, QUAD>),
     static_assert(W == QK_GROUP || (DUAL && G == 1 && W % FP == 0 && W <= QK_GROUP), "group width");
     static_assert(!QUAD || (DUAL && G == 1 && W % 16 == 0), "quad backs: dual chain, one group");
     constexpr int kGroups = G, kFrontPer = FP;
-    constexpr int kBackWaves = kBackWavesOf<G, FP, MODE, DUAL, W, QUAD>;
+    constexpr int kBackWaves = kBackWavesOf<G, DUAL, W, QUAD>;
     constexpr int kChainWaves = QUAD ? W / 16 : 1;     // back waves per frame chain and group
-    constexpr bool kDyn = DUAL && (QPSK_DYNPRIO == 2 || (QPSK_DYNPRIO == 1 && QUAD));
+    // dynamic issue priority of the dual-chain back waves: they train at the
+    // highest priority unless another back wave waits for its fronts.  Quad
+    // backs only (-1.5% at 8,192 channels, -4% at 4,096; lane backs +1..4%:
+    // profiles/r03_dynprio_ab.txt)
+    constexpr bool kDyn = DUAL && QUAD;
     constexpr int kFrontCh = W / kFrontPer;            // channels per front wave
     constexpr int kFrontWaves = kGroups * kFrontPer;
-    constexpr int kBlock = 64 * (kBackWaves + kFrontWaves);
+    constexpr int kBlock = 64 * kWavesOf<G, FP, DUAL, W, QUAD>;
     const RxArgs a{in, hist, ptab, ks, win0, win1, mi0, mi1, rt0, rt1, bits, valid, trace, soft,
                    jobs, njobs, nch, F, g0, (size_t)jcap, roles, err,
                    // HP (reference mode only): fft_tab carries the head pre-pass outputs
@@ -1648,8 +1543,12 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, MODE, DUAL, W, QUAD>),
     __shared__ int mi_s[kGroups][2][QK_GROUP], rt_s[kGroups][2][QK_GROUP];
     // hunt tables: the MFMA correlator's B, or the FFT hunt's twiddles / Q / permutation
     __shared__ __attribute__((aligned(16))) float BT[(MODE & 2) ? kFftHT : kHuntTab];
-    // the split FIR's pass-2 lane map (kSplitTab; 2 KB, reference mode only)
-    constexpr bool kSplitK = MODE == 0 && !HP && QPSK_FIR_SPLIT && (!DUAL || QPSK_FIR_SPLIT == 2);
+    // the 4x2 kernel in reference mode (not the head pre-pass, not the FFT
+    // hunt) runs the split FIR (fir_split); the dual-chain shapes keep fir_dec +
+    // fir_head_at: their fronts are latency-bound and the split's extra LDS
+    // reads cost them ~1% (profiles/r05_split_ab.txt).  Its pass-2 lane map
+    // (kSplitTab; 2 KB):
+    constexpr bool kSplitK = MODE == 0 && !HP && !DUAL;
     __shared__ uint32_t p2w[kSplitK ? kSplitTabWords : 1];
     const uint8_t* p2tab = reinterpret_cast<const uint8_t*>(p2w);
     // DUAL progress counters, per group, frame parity and channel block (one
@@ -1692,17 +1591,13 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, MODE, DUAL, W, QUAD>),
     TAIL_INIT();
     for (int i = threadIdx.x; i < QK_FRAME / 2; i += kBlock)
         reinterpret_cast<float4*>(P)[i] = reinterpret_cast<const float4*>(a.ptab)[i];
-    if constexpr (kSplitK && QPSK_SPLIT_BANKS)
+    if constexpr (kSplitK)
         for (int i = threadIdx.x; i < kSplitTabWords; i += kBlock)
             p2w[i] = reinterpret_cast<const uint32_t*>(&kSplitTab)[i];
     if constexpr ((MODE & 2) != 0) {
         for (int i = threadIdx.x; i < kFftHT; i += kBlock) BT[i] = fft_tab[i];
     } else {
-#if QPSK_HUNT_FILTER
         qhunt::bconst_h_lds(threadIdx.x, kBlock, BT);
-#else
-        qhunt::bconst_lds(threadIdx.x, kBlock, BT);
-#endif
     }
     if (wave < kGroups) {   // per-channel state of the groups at the call's first frame
         const int ch = (grp0 + wave) * W + lane;
@@ -1743,7 +1638,7 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, MODE, DUAL, W, QUAD>),
             const int ch = (grp0 + gi) * W + idx;
             const bool live = own && ch < a.nch;
             if (kDyn || ((a.roles >> 4) & 3) == 2) __builtin_amdgcn_s_setprio(2);
-            // kDyn (QPSK_DYNPRIO): every 4 training steps, drop to the lowest
+            // kDyn: every 4 training steps, drop to the lowest
             // issue priority while another back wave waits for its fronts, else the highest
             auto poll = [&] {
                 if constexpr (kDyn) {
@@ -1818,12 +1713,14 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, MODE, DUAL, W, QUAD>),
             auto blive = [&](int bb) { return max(0, min(mych, a.nch - bch0(bb))); };
             float2* M = Ms[f];
             int pf[kPf<DM>];
-            // QPSK_FIR_SPLIT == 2 (A/B knob): the split FIR here too
-            constexpr bool kSplitD = MODE == 0 && !HP && QPSK_FIR_SPLIT == 2;
-            constexpr int kFrD = kSplitD ? QPSK_FRESH_SPLIT : QPSK_FRESH;
+            // the dual-chain fronts keep fir_dec + fir_head_at (see kSplitK).  A named
+            // constant like the 4x2 fronts' kSplit, not a literal: the quad
+            // kernels' frame_iter lambda names it, and without that their
+            // register allocation comes out differently
+            constexpr bool kSplitD = false;
             if (kDyn) __builtin_amdgcn_s_setprio(1);
             else if (((a.roles >> 4) & 3) == 1) __builtin_amdgcn_s_setprio(2);
-            if (blive(0) > 0) prefetch<DM, false, kFrD>(srcs(a, bch0(0), 0), lane, pf);
+            if (blive(0) > 0) prefetch<DM, false, kSplitD>(srcs(a, bch0(0), 0), lane, pf);
             // diagnostic stamps (QPSK_STAMPS): 7 wait for the backs, 0 mix,
             // 4 window store, 1 prefetch, 8-12 front_channel phases, 6 its tail,
             // 5 signal
@@ -1849,7 +1746,7 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, MODE, DUAL, W, QUAD>),
             for (int c = 0; c < nl; c++, k++) {                                                                \
                 const int ch = c0 + c;                                                                         \
                 float2* dcur = decs[f][k % kDecBuf];                                                           \
-                mix<DM, kFrD>(lane, pf, g, P, M);                                                              \
+                mix<DM, kSplitD>(lane, pf, g, P, M);                                                           \
                 STAMP(0);                                                                                      \
                 if (c > 0)                                                                                     \
                     store_window(lane, pmi, decs[f][(k - 1) % kDecBuf], wout + (size_t)(ch - 1) * kWinStride); \
@@ -1862,7 +1759,7 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, MODE, DUAL, W, QUAD>),
                         while (nb < kChainWaves && blive(nb) == 0) nb++;                                       \
                         if (nb == kChainWaves) { nb = 0; nn = n + 1; }                                         \
                     }                                                                                          \
-                    if (nn < a.F) prefetch<DM, CG, kFrD>(srcs(a, bch0(nb) + nc, nn), lane, pf);                \
+                    if (nn < a.F) prefetch<DM, CG, kSplitD>(srcs(a, bch0(nb) + nc, nn), lane, pf);             \
                 }                                                                                              \
                 wave_lds_sync();                                                                               \
                 STAMP(1);                                                                                      \
@@ -1942,8 +1839,7 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, MODE, DUAL, W, QUAD>),
         // channel's window -> prefetch the next channel -> FIR/correlate/argmax
         // the split FIR (fir_split) and, to keep the channel loop's per-lane
         // constants out of scratch beside it, recomputed prefetch offsets
-        constexpr bool kSplit = MODE == 0 && !HP && QPSK_FIR_SPLIT;
-        constexpr int kFr = kSplit ? QPSK_FRESH_SPLIT : QPSK_FRESH;
+        constexpr bool kSplit = MODE == 0 && !HP;
         const int f = wave - kBackWaves;
         const int gi = f / kFrontPer;
         const int cbeg = (f % kFrontPer) * kFrontCh;
@@ -1953,7 +1849,7 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, MODE, DUAL, W, QUAD>),
         const bool on = (a.roles & 2) != 0 && nlive > 0;
         if (((a.roles >> 4) & 3) == 1) __builtin_amdgcn_s_setprio(2);
         int pf[kPf<DM>];
-        if (on) prefetch<DM, false, kFr>(srcs(a, ch0, 0), lane, pf);
+        if (on) prefetch<DM, false, kSplit>(srcs(a, ch0, 0), lane, pf);
         STAMP_DECL
         for (int n = 0; n < a.F; n++) {
             const int p = n & 1;
@@ -1969,18 +1865,18 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, MODE, DUAL, W, QUAD>),
             for (int c = 0; on && c < nlive; c++) {
                 const int ch = ch0 + c;
                 float2* dcur = decs[f][c % kDecBuf];
-                // QPSK_LATE_YIELD (A/B knob): the last K channels of a frame at
-                // the back wave's issue priority, so the back (the frame's last
-                // wave) gets its share before the fronts reach the barrier
-                if (QPSK_LATE_YIELD > 0 && c == nlive - QPSK_LATE_YIELD && ((a.roles >> 4) & 3) == 1)
+                // the last kLateYield channels of a frame at the back wave's
+                // issue priority, so the back (the frame's last wave) gets its
+                // share before the fronts reach the barrier
+                if (c == nlive - kLateYield && ((a.roles >> 4) & 3) == 1)
                     __builtin_amdgcn_s_setprio(0);
-                mix<DM, kFr>(lane, pf, g, P, M);
+                mix<DM, kSplit>(lane, pf, g, P, M);
                 STAMP(0);
                 if (c > 0) store_window(lane, pmi, decs[f][(c - 1) % kDecBuf], wout + (size_t)(ch - 1) * kWinStride);
                 {   // next channel of this frame, else the first of the next frame
                     const bool same = c + 1 < nlive;
                     if (same || n + 1 < a.F)
-                        prefetch<DM, false, kFr>(srcs(a, same ? ch + 1 : ch0, same ? n : n + 1), lane, pf);
+                        prefetch<DM, false, kSplit>(srcs(a, same ? ch + 1 : ch0, same ? n : n + 1), lane, pf);
                 }
                 wave_lds_sync();
                 STAMP(1);
@@ -1993,7 +1889,7 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, MODE, DUAL, W, QUAD>),
             }
             TAIL_ARRIVE();
             __syncthreads();
-            if (QPSK_LATE_YIELD > 0 && ((a.roles >> 4) & 3) == 1) __builtin_amdgcn_s_setprio(2);
+            if (((a.roles >> 4) & 3) == 1) __builtin_amdgcn_s_setprio(2);
             STAMP(7);
         }
         STAMP_FLUSH();
@@ -2011,12 +1907,23 @@ float bits2f(uint32_t u) {
 
 }  // namespace
 
-// rx_kernel instantiations (pick_shape below)
+// rx_kernel instantiations (pick_shape below); ShapeOf<kind> holds a kind's
+// template parameters, the only place that spells them
 struct Shape {
     enum Kind { k4x2, k2x4d, k1x8d64, k1x8q16, k1x8q32 };
     int kind;
     int roles;
 };
+template <int KIND> struct ShapeOf;
+template <int G_, int FP_, bool DUAL_, int W_, bool QUAD_> struct ShapeParams {
+    static constexpr int G = G_, FP = FP_, W = W_;
+    static constexpr bool DUAL = DUAL_, QUAD = QUAD_;
+};
+template <> struct ShapeOf<Shape::k4x2> : ShapeParams<4, 2, false, 64, false> {};
+template <> struct ShapeOf<Shape::k2x4d> : ShapeParams<2, 4, true, 64, false> {};
+template <> struct ShapeOf<Shape::k1x8d64> : ShapeParams<1, 8, true, 64, false> {};
+template <> struct ShapeOf<Shape::k1x8q16> : ShapeParams<1, 8, true, 16, true> {};
+template <> struct ShapeOf<Shape::k1x8q32> : ShapeParams<1, 8, true, 32, true> {};
 
 // front stagger, 512-cycle units (roles bits 8-15): round 1 measured 12 as
 // -0.7%; on round 5's kernels 0 is -0.4% (profiles/r05_stagger_ab.txt)
@@ -2469,10 +2376,12 @@ extern "C" uint64_t qpsk_rx_frames(const qpsk_ctx* c) { return c ? c->frames : 0
 //     with back priority and 2 channels moved off each front wave that
 //     shares a SIMD with a back wave (-3%, profiles/r01_split_ab.txt).
 // QPSK_SHAPE (4x2 | 2x4d | 1x8) and QPSK_WIDTH force a shape for tests and A/B
-// runs.  Measured and dropped (records in profiles/, DESIGN.md "Measured and
-// not kept"): 4x1d, 2x4 and 1x8 with single back waves, the early-terminated
-// flow kernel (r01_flow_ab.txt), lane backs at W = 16 / 32, one front per SIMD
-// (1x4) and the 4x3 C3 shape (round 5 removed the last three from the build).
+// runs.  The result is a Shape::Kind; launch_shape maps it to the kernel whose
+// parameters ShapeOf gives that kind.  Measured and dropped (records in
+// profiles/, DESIGN.md "Measured and not kept"): 4x1d, 2x4 and 1x8 with single
+// back waves, the early-terminated flow kernel (r01_flow_ab.txt), lane backs at
+// W = 16 / 32, one front per SIMD (1x4) and the 4x3 C3 shape (round 5 removed
+// the last three from the build).
 static Shape pick_shape(const qpsk_ctx* c) {
     Shape sh{c->shape, c->roles};
     if (sh.kind < 0)
@@ -2488,6 +2397,49 @@ static Shape pick_shape(const qpsk_ctx* c) {
     }
     if (c->prio >= 0) sh.roles = (sh.roles & ~(3 << 4)) | (c->prio << 4);
     return sh;
+}
+
+// What a call passes to rx_kernel beside the context's own buffers
+struct RxCall {
+    const int16_t* in;
+    int F;
+    uint8_t *bits, *valid;
+    int32_t* trace;
+    float* soft;
+    hipStream_t s;
+    int* err;
+    int parity;
+    unsigned g0;
+    int roles;
+};
+
+// rx_kernel of one shape, mode and head-pass setting.  Grid and block come from
+// the parameters the kernel is instantiated with: a workgroup serves G groups
+// of W channels with kWavesOf waves (less c->short_block, the launch-shape
+// guard's test hook).
+template <int KIND, int MODE, bool HP>
+static void launch_rx(const qpsk_ctx* c, const RxCall& a) {
+    using S = ShapeOf<KIND>;
+    constexpr size_t kPer = (size_t)S::G * S::W;
+    constexpr int kBlock = 64 * kWavesOf<S::G, S::FP, S::DUAL, S::W, S::QUAD>;
+    hipLaunchKernelGGL((rx_kernel<S::G, S::FP, MODE, S::DUAL, S::W, S::QUAD, HP>),
+                       dim3((unsigned)((c->nch + kPer - 1) / kPer)), dim3(kBlock - c->short_block), 0,
+                       a.s, a.in, c->d_hist, c->d_ptab, c->d_ks, c->d_win[0], c->d_win[1], c->d_mi[0],
+                       c->d_mi[1], c->d_rt[0], c->d_rt[1], a.bits, a.valid, a.trace,
+                       reinterpret_cast<float2*>(a.soft), c->d_jobs, c->d_njobs + a.parity, c->nch, a.F,
+                       a.g0, a.roles, HP ? reinterpret_cast<const float*>(c->d_heads) : c->d_fft,
+                       (unsigned long long)c->jobs_cap, a.err);
+}
+
+template <int MODE, bool HP>
+static void launch_shape(int kind, const qpsk_ctx* c, const RxCall& a) {
+    switch (kind) {
+        case Shape::k2x4d: return launch_rx<Shape::k2x4d, MODE, HP>(c, a);
+        case Shape::k1x8d64: return launch_rx<Shape::k1x8d64, MODE, HP>(c, a);
+        case Shape::k1x8q16: return launch_rx<Shape::k1x8q16, MODE, HP>(c, a);
+        case Shape::k1x8q32: return launch_rx<Shape::k1x8q32, MODE, HP>(c, a);
+        default: return launch_rx<Shape::k4x2, MODE, HP>(c, a);
+    }
 }
 
 // The two launches of a call (qpsk_rx_batch_device), with the device error word
@@ -2547,45 +2499,22 @@ int qpsk_rx_launch(qpsk_ctx* c, const int16_t* d_in, int F, uint8_t* d_bits, uin
     const unsigned g0 = (unsigned)(c->frames % (uint64_t)(2 * QK_KS_FRAMES));
     Shape sh = pick_shape(c);
     if (c->stall_calls >= 0 && c->launches >= (uint64_t)c->stall_calls) sh.roles &= ~kDebugStall;
-#define QPSK_LAUNCH(GG, FF, MM, DD, WW, QQ, HH)                                                \
-    hipLaunchKernelGGL((rx_kernel<GG, FF, MM, DD, WW, QQ, HH>),                                \
-                       dim3((unsigned)((c->nch + (size_t)GG * WW - 1) / ((size_t)GG * WW))),   \
-                       dim3(64 * (kBackWavesOf<GG, FF, MM, DD, WW, QQ> + (GG) * (FF)) - c->short_block), 0, s, \
-                       d_in, c->d_hist, c->d_ptab,                                             \
-                       c->d_ks, c->d_win[0], c->d_win[1], c->d_mi[0], c->d_mi[1], c->d_rt[0],  \
-                       c->d_rt[1], d_bits, d_valid, d_trace, reinterpret_cast<float2*>(d_soft), \
-                       c->d_jobs, c->d_njobs + parity, c->nch, F,                               \
-                       g0, sh.roles,                                                           \
-                       HH ? reinterpret_cast<const float*>(c->d_heads) : c->d_fft,             \
-                       (unsigned long long)c->jobs_cap, d_err)
-#define QPSK_LAUNCH_SHAPES(MM, HH)                                                             \
-    do {                                                                                       \
-        switch (sh.kind) {                                                                     \
-            case Shape::k2x4d: QPSK_LAUNCH(2, 4, MM, true, 64, false, HH); break;              \
-            case Shape::k1x8d64: QPSK_LAUNCH(1, 8, MM, true, 64, false, HH); break;            \
-            case Shape::k1x8q16: QPSK_LAUNCH(1, 8, MM, true, 16, true, HH); break;             \
-            case Shape::k1x8q32: QPSK_LAUNCH(1, 8, MM, true, 32, true, HH); break;             \
-            default: QPSK_LAUNCH(4, 2, MM, false, 64, false, HH); break;                       \
-        }                                                                                      \
-    } while (0)
-#define QPSK_LAUNCH_MODE(MM) QPSK_LAUNCH_SHAPES(MM, false)
+    const RxCall call{d_in, F, d_bits, d_valid, d_trace, d_soft, s, d_err, parity, g0, sh.roles};
     if (hp) {   // head pre-pass: every channel-frame's F_{n+1}, then the frame loop
         const size_t ncf = (size_t)c->nch * (size_t)F;
         hipLaunchKernelGGL(head_kernel, dim3((unsigned)((ncf + 3) / 4)), dim3(256), 0, s, d_in,
                            c->d_hist, c->d_ptab, c->d_heads, c->nch, F,
                            g0);
         HCHECK(hipGetLastError());
-        QPSK_LAUNCH_SHAPES(0, true);
-    } else
-    switch (c->mode) {
-        case 0: QPSK_LAUNCH_MODE(0); break;
-        case 1: QPSK_LAUNCH_MODE(1); break;
-        case 2: QPSK_LAUNCH_MODE(2); break;
-        default: QPSK_LAUNCH_MODE(3); break;
+        launch_shape<0, true>(sh.kind, c, call);
+    } else {
+        switch (c->mode) {
+            case 0: launch_shape<0, false>(sh.kind, c, call); break;
+            case 1: launch_shape<1, false>(sh.kind, c, call); break;
+            case 2: launch_shape<2, false>(sh.kind, c, call); break;
+            default: launch_shape<3, false>(sh.kind, c, call); break;
+        }
     }
-#undef QPSK_LAUNCH_MODE
-#undef QPSK_LAUNCH_SHAPES
-#undef QPSK_LAUNCH
     HCHECK(hipGetLastError());
     if (slot >= 0) HCHECK(hipEventRecord(c->ev[slot][1], s));
     // at most one job per channel-frame: a small call (the per-frame drop-in
@@ -2694,11 +2623,8 @@ static Stage stage_of(size_t cf) {
 // calls up to this many input bytes stage through pinned memory
 constexpr size_t kPinnedStage = (size_t)8 << 20;
 // calls up to this many channel-frames (the drop-in qpsk_rx_frame: one) run
-// their kernels on the pinned block itself, no copies (QPSK_ZERO_COPY A/B knob)
-#ifndef QPSK_ZERO_COPY
-#define QPSK_ZERO_COPY 64
-#endif
-constexpr size_t kZeroCopyCF = QPSK_ZERO_COPY;
+// their kernels on the pinned block itself, no copies
+constexpr size_t kZeroCopyCF = 64;
 
 static int stage_grow(qpsk_ctx* c, size_t F) {
     if (F <= c->s_frames) return QPSK_OK;

@@ -102,3 +102,25 @@ def test_variant_flags_change_the_hash_and_force_a_rebuild():
     dry = _make("-n", "QPSK_VARIANT=-DQPSK_FIR_NOMASK=1")
     assert "qpsk_rx.hip" in dry.stdout and "QPSK_FIR_NOMASK" in dry.stdout
     assert "qpsk_rx.hip" not in _make("-n").stdout
+
+
+def _syntax_only(*defs):
+    import subprocess
+    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+    inc = os.path.abspath(os.path.join(os.path.dirname(CSRC), "..", "include"))
+    return subprocess.run([hipcc, "--cuda-host-only", "-fsyntax-only", "-std=c++17", f"-I{inc}", f"-I{CSRC}",
+                           *defs, os.path.join(CSRC, "qpsk_rx.hip")], capture_output=True, text=True)
+
+
+@pytest.mark.parametrize("knob", ["QPSK_FIR_SPLIT=2", "QPSK_HUNT_OVERLAP=0"])
+def test_a_removed_knob_stops_the_build(knob):
+    """The compile-time A/B knobs whose alternative branches are gone (DESIGN.md
+    "Removed knobs") must not be accepted in silence: a variant script that
+    still passes one would compare HEAD with itself.  qpsk_rx.hip refuses any
+    of them with an #error that names it (QPSK_HUNT_OVERLAP was qpsk_hunt.h's,
+    which qpsk_rx.hip includes); a knob that is still there passes."""
+    r = _syntax_only(f"-D{knob}")
+    assert r.returncode != 0
+    assert "error:" in r.stderr and knob.split("=")[0] in r.stderr
+    ok = _syntax_only("-DQPSK_STAMPS")
+    assert ok.returncode == 0, ok.stderr
