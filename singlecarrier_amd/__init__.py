@@ -2,7 +2,8 @@
 
 Python mirror of the C-ABI in ``include/qpsk_internal.h`` (the reference's
 ``headers/qpsk_internal.h:79-84`` surface) and ``include/qpsk_batch.h`` (the
-batched, multi-channel receiver), over ``singlecarrier_amd/libqpsk_hip.so``.
+batched, multi-channel receiver) and ``include/qpsk_tx.h`` (the batched
+transmitter), over ``singlecarrier_amd/libqpsk_hip.so``.
 
 There is no CPU fallback: if the HIP library is missing or no GPU is present,
 the receive functions raise.  (The CPU restatement in ``oracle/`` is test
@@ -147,6 +148,21 @@ def lib():
         L.qpsk_rx_state_size.argtypes = [i32]
         L.qpsk_rx_state_save.argtypes = [vp, i32, i32, vp, C.c_size_t]
         L.qpsk_rx_state_load.argtypes = [vp, i32, i32, vp, C.c_size_t]
+        L.qpsk_tx_create.restype = vp
+        L.qpsk_tx_create.argtypes = [i32, i32, i32, C.POINTER(C.c_int)]
+        L.qpsk_tx_destroy.restype = None
+        L.qpsk_tx_destroy.argtypes = [vp]
+        L.qpsk_tx_reset.argtypes = [vp]
+        L.qpsk_tx_channels.argtypes = [vp]
+        L.qpsk_tx_gap.argtypes = [vp]
+        L.qpsk_tx_packets.restype = u64
+        L.qpsk_tx_packets.argtypes = [vp]
+        L.qpsk_tx_batch.argtypes = [vp, vp, i32, vp, C.c_long]
+        L.qpsk_tx_batch_device.argtypes = [vp, vp, i32, vp, C.c_long, vp]
+        L.qpsk_tx_sync.argtypes = [vp]
+        L.qpsk_tx_batch_host.argtypes = [vp, i32, vp, i32, i32, vp, C.c_long, i32]
+        L.qpsk_tx_state_init.restype = None
+        L.qpsk_tx_state_init.argtypes = [vp]
         L.cnormf.restype = C.c_float
         L.cnormf.argtypes = [_CF]   # _Complex float == {float, float} in one SSE reg (SysV)
         _lib = L
@@ -164,7 +180,10 @@ SYMBOLS = ["qpsk_rx_create", "qpsk_rx_create_mode", "qpsk_rx_mode", "qpsk_rx_des
            "qpsk_stream_acquire", "qpsk_stream_submit", "qpsk_stream_pending",
            "qpsk_stream_retrieve", "qpsk_stream_ctx", "qpsk_records", "qpsk_fft_alloc",
            "qpsk_fft_free", "qpsk_fft_device", "qpsk_fft", "qpsk_rx_state_size",
-           "qpsk_rx_state_save", "qpsk_rx_state_load"]
+           "qpsk_rx_state_save", "qpsk_rx_state_load",
+           "qpsk_tx_create", "qpsk_tx_destroy", "qpsk_tx_reset", "qpsk_tx_channels", "qpsk_tx_gap",
+           "qpsk_tx_packets", "qpsk_tx_batch", "qpsk_tx_batch_device", "qpsk_tx_sync",
+           "qpsk_tx_batch_host"]
 
 
 def _check(rc: int) -> None:
@@ -293,6 +312,112 @@ class Receiver:
             stream = torch.cuda.current_stream(x.device)
         _check(lib().qpsk_rx_batch_device(self._h, _ptr(x), nf, _ptr(bits), _ptr(valid),
                                           _ptr(trace), _ptr(soft), C.c_void_p(stream.cuda_stream)))
+
+
+TX_PACKET = 1880         # transmitted samples per packet: 5 * (128 + 8 * 31)
+PACKET_BITS = 8 * NBITS  # payload bytes per packet, uint8 [8][62]
+TX_STATE_SIZE = (49 * 2 + 2) * 4   # sizeof(qpsk_tx_state), include/qpsk_synth.h
+
+
+def _tx_bits(bits, nch=None):
+    bits = np.ascontiguousarray(bits, dtype=np.uint8)
+    if bits.ndim != 4 or bits.shape[2:] != (8, NBITS) or (nch is not None and bits.shape[0] != nch):
+        raise ValueError(f"expected uint8 [{nch or 'nch'}][npackets][8][{NBITS}], got {bits.shape}")
+    return bits
+
+
+class Transmitter:
+    """A batch of ``nch`` independent transmitters on one GPU (``qpsk_tx_ctx``,
+    include/qpsk_tx.h).
+
+    Each channel is the reference transmitter in the packet order of its
+    main() (src/qpsk.c:380-413) with the caller's payload bits; ``gap`` zero
+    samples follow every packet.  State persists across calls.  Like
+    ``Receiver`` there is no CPU fallback: without a GPU the constructor raises
+    (``tx_batch_host`` is the explicit host path).
+    """
+
+    def __init__(self, nch: int, device: int = 0, gap: int = 903):
+        err = C.c_int(0)
+        self._h = lib().qpsk_tx_create(device, nch, gap, C.byref(err))
+        if not self._h:
+            _check(err.value or -3)
+        self.nch, self.device, self.gap = nch, device, gap
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().qpsk_tx_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self) -> None:
+        _check(lib().qpsk_tx_reset(self._h))
+
+    def sync(self) -> None:
+        _check(lib().qpsk_tx_sync(self._h))
+
+    def packets(self) -> int:
+        return int(lib().qpsk_tx_packets(self._h))
+
+    def modulate(self, bits) -> np.ndarray:
+        """Host arrays: bits uint8 [nch][npackets][8][62] -> int16
+        [nch][npackets * (1880 + gap)]."""
+        bits = _tx_bits(bits, self.nch)
+        npk = bits.shape[1]
+        out = np.zeros((self.nch, npk * (TX_PACKET + self.gap)), np.int16)
+        _check(lib().qpsk_tx_batch(self._h, _ptr(bits), npk, _ptr(out), out.shape[1]))
+        return out
+
+    def modulate_device(self, bits, out, stream=None) -> None:
+        """Device tensors (torch, on this device): bits uint8 [nch][npackets][8][62]
+        contiguous, out int16 [nch][>= npackets * (1880 + gap)] with unit stride
+        along a row and ld = out.stride(0).  Enqueues on ``stream`` (default:
+        torch's current stream) and returns without synchronising."""
+        import torch
+        if bits.dtype != torch.uint8 or bits.dim() != 4 or bits.shape[0] != self.nch \
+                or tuple(bits.shape[2:]) != (8, NBITS) or not bits.is_contiguous() or not bits.is_cuda:
+            raise ValueError("bits must be a contiguous cuda uint8 [nch][npackets][8][62] tensor")
+        npk = bits.shape[1]
+        if out.dtype != torch.int16 or out.dim() != 2 or out.shape[0] != self.nch or not out.is_cuda \
+                or out.shape[1] < npk * (TX_PACKET + self.gap) \
+                or (out.shape[1] > 1 and out.stride(1) != 1):
+            raise ValueError("out must be a cuda int16 [nch][>= npackets * (1880 + gap)] tensor "
+                             "with unit stride along a row")
+        ld = out.stride(0) if self.nch > 1 else max(out.stride(0), out.shape[1])
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device)
+        _check(lib().qpsk_tx_batch_device(self._h, _ptr(bits), npk, _ptr(out), ld,
+                                          C.c_void_p(stream.cuda_stream)))
+
+
+def tx_states(nch: int) -> np.ndarray:
+    """nch transmitter states (qpsk_tx_state) in main()'s start state, as uint8
+    [nch][TX_STATE_SIZE]."""
+    st = np.zeros((nch, TX_STATE_SIZE), np.uint8)
+    for c in range(nch):
+        lib().qpsk_tx_state_init(st[c].ctypes.data)
+    return st
+
+
+def tx_batch_host(bits, gap: int = 903, states=None, threads: int = 0) -> np.ndarray:
+    """qpsk_tx_batch_host: the batched transmitter's contract on the host.
+    bits uint8 [nch][npackets][8][62] -> int16 [nch][npackets * (1880 + gap)].
+    ``states`` (tx_states(nch)) is advanced in place, so a stream may continue
+    over calls; None starts every channel fresh."""
+    bits = _tx_bits(bits)
+    nch, npk = bits.shape[:2]
+    if states is None:
+        states = tx_states(nch)
+    if states.dtype != np.uint8 or states.shape != (nch, TX_STATE_SIZE) or not states.flags.c_contiguous:
+        raise ValueError(f"states must be tx_states({nch})")
+    if gap < 0:
+        _check(QPSK_EINVAL)
+    out = np.zeros((nch, npk * (TX_PACKET + gap)), np.int16)
+    threads = threads or min(16, os.cpu_count() or 1)
+    _check(lib().qpsk_tx_batch_host(_ptr(states), nch, _ptr(bits), npk, gap, _ptr(out),
+                                    out.shape[1], threads))
+    return out
 
 
 # --- the reference's single-channel surface (headers/qpsk_internal.h:79-84) ---

@@ -34,6 +34,7 @@
 
 #include "qpsk_consts.h"
 #include "qpsk_synth.h"
+#include "qpsk_tx_internal.h"
 
 #pragma clang fp contract(off)
 
@@ -143,9 +144,16 @@ __global__ void __launch_bounds__(256) noise_kernel(uint64_t seed, uint32_t c0, 
 // 640 (preamble) and 155 (data) samples in packet order.  Same fp32 operations
 // as qpsk_tx_frame_state() (qpsk_surface.c).
 extern "C" void qpsk_tx_phase_table(float* out2, long ntx) {
+    float ph[2] = {1.0f, 0.0f};   // fbb_tx_phase = cmplx(0.0f), src/qpsk.c:375
+    qpsk_tx_phase_run(out2, ntx, ph);
+}
+
+// The same loop from a carried phase (qpsk_tx_internal.h): the batched
+// transmitter (qpsk_tx.hip) continues a stream over any number of calls.
+extern "C" void qpsk_tx_phase_run(float* out2, long ntx, float ph[2]) {
     const float arg = (float)(2.0f * 3.14159265358979323846 * 1100.0f / 8000.0f);
     const float rr = cosf(arg), ri = sinf(arg);
-    float pr = 1.0f, pi = 0.0f;
+    float pr = ph[0], pi = ph[1];
     long t = 0;
     for (int call = 0; t < ntx; call = (call + 1) % 9) {
         const int len = call == 0 ? 5 * QK_NPRE : 5 * QK_NDSYM;
@@ -161,6 +169,8 @@ extern "C" void qpsk_tx_phase_table(float* out2, long ntx) {
         pr = pr / mag;
         pi = pi / mag;
     }
+    ph[0] = pr;
+    ph[1] = pi;
 }
 
 extern "C" int qpsk_synth_device(uint64_t seed, uint32_t c0, int nch, double ebn0_db,

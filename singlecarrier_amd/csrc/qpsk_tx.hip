@@ -1,0 +1,455 @@
+// qpsk_tx.hip -- the batched transmitter of include/qpsk_tx.h on the GPU:
+// qpsk_tx_frame (src/qpsk.c:278-322) in the packet order of the reference's
+// main() (src/qpsk.c:380-413) for many channels with caller-supplied payload
+// bits, bit-identical to the host twin qpsk_tx_batch_host (qpsk_tx_host.c).
+//
+// What a sample depends on (DESIGN.md "Batched transmitter"):
+//   * a channel's row is one flat stream of npackets * P samples, P = 1880 +
+//     gap; position p is packet k = p / P, offset r = p % P; r >= 1880 is gap
+//     (zero, never filtered: the reference fwrites it), otherwise it is TX
+//     sample t = 1880 k + r of the call;
+//   * the FIR input is the zero-stuffed symbol stream, so sample t is the sum
+//     over the <= 10 symbols S - 9 .. S (S = t / 5) of +-QK_RRC[i], i ascending
+//     (one packed fma per tap: see period());
+//     symbols before a packet's first are the previous packet's last 9
+//     whatever the gap, taken from the payload when that packet is in this
+//     call, from the saved per-channel state otherwise, and zero before the
+//     context's first packet;
+//   * the carrier depends on the transmitter's call sequence only: the host
+//     continues the reference's fp32 recurrence from the carried phase and
+//     uploads one float2 per TX sample of the call.
+//
+// Shape.  The arithmetic wants a thread to own one symbol period (5 samples
+// whose tap indices are compile-time constants); the stores want a lane to own
+// 8 consecutive samples at a 16-byte-aligned address.  P is odd for the
+// reference gap and ld and out are the caller's, so the two never line up:
+// the block computes into an LDS tile (ds_write_b16) and stores from it
+// (ds_read_b128 -> global_store_dwordx4).  A block owns kTile samples of the
+// row, cut at 16-byte-aligned addresses, and loops over kLoop channels of one
+// alignment class (c mod 8: rows 8 apart differ by 8 ld samples, so they share
+// out + c ld mod 16 bytes).  Everything that does not depend on the channel --
+// (k, r), the LDS slot, the scale and the 5 carrier values of each period --
+// is worked out once and kept in registers over that loop; per channel only
+// the payload changes: its bytes are read once per tile, reduced to one sign
+// bit per component with ballots, and kept in LDS as two bit strings.  Gap
+// positions of the tile are zeroed once and never overwritten, so the same
+// store pass writes the gap.  Row heads and tails that do not fill an aligned
+// 16 bytes are stored per int16.
+#include <hip/hip_runtime.h>
+
+#include <new>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "qpsk_consts.h"
+#include "qpsk_tx.h"
+#include "qpsk_tx_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kTxPacket = 1880;    // transmitted samples per packet
+constexpr int kSymPacket = 376;    // 128 + 8*31 symbols per packet
+constexpr int kPacketBits = 496;   // payload bytes per packet
+constexpr int kHist = 9;           // earlier symbols a sample's FIR window reaches
+constexpr int kThreads = 256;
+constexpr int kChunk = 8;                    // samples per 16-byte store
+constexpr int kTile = kThreads * kChunk;     // samples of a row per block
+constexpr int kMargin = 8;         // LDS slots either side of the tile: a period that straddles
+                                   // the tile's edge is written whole, its outside part never read
+constexpr int kClasses = 8;        // alignment classes: (out + c*ld) mod 16 bytes repeats every 8 rows
+constexpr int kLoop = 16;          // channels of one class a block loops over
+constexpr int kRounds = 2;         // periods per thread: kTile/5 + 2 <= kRounds * kThreads
+constexpr int kSignBits = kRounds * kThreads;   // sign bits per channel and component, 64 per ballot
+constexpr int kSignWords = kSignBits / 32 + 1;  // + one zero word: a window read may touch it
+static_assert(kTile / 5 + 2 <= kRounds * kThreads, "a tile's periods must fit the rounds");
+static_assert(kTile / 5 + 2 + kHist <= kSignBits, "and their symbols the bit strings");
+static_assert(kMargin >= 4 && kMargin % kChunk == 0, "margin keeps the 16-byte LDS reads aligned");
+
+// bit u set: preamble symbol u is -1 (both components, src/qpsk.c:361-365)
+constexpr unsigned long long pre_neg(int half) {
+    unsigned long long m = 0;
+    for (int i = 0; i < 64; i++)
+        if (QK_PRE[half * 64 + i] < 0) m |= 1ull << i;
+    return m;
+}
+
+__host__ __device__ inline long lmin(long a, long b) { return a < b ? a : b; }
+
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+// One symbol period (5 samples) of one channel into the LDS tile.
+//   wi, wq   bit j = sign of symbol S - 9 + j (1: -1), j = 0 .. 9
+//   live     kZeros only: bit j clear = that symbol is before the stream's
+//            first (a zero in tx_filter)
+//   ph       carrier of the period's 5 samples; scale 8192 (preamble) or 16384
+// fir(): y = sum_i mem[i]*c[i], i ascending (src/fir.c:36-42), where only the
+// symbol instants are nonzero: sample jj of the period has symbol S - m at tap
+// i = 48 - jj - 5 m.  The reference rounds twice per tap, mem*c and y + that;
+// mem is +-1 (or 0), so the product is exact and fma(mem, c, y), which rounds
+// mem*c + y once, is the same fp32 value: an explicit fma here is not a
+// contraction that changes a result.  (re, im) ride one packed instruction.
+template <bool kZeros>
+__device__ inline void period(uint32_t wi, uint32_t wq, uint32_t live, const float2 (&ph)[5],
+                              float scale, int16_t* dst) {
+    v2f s[10];
+#pragma unroll
+    for (int j = 0; j < 10; j++) {
+        uint32_t a = ((wi << (31 - j)) & 0x80000000u) | 0x3f800000u;   // -1.0f or 1.0f
+        uint32_t b = ((wq << (31 - j)) & 0x80000000u) | 0x3f800000u;
+        if (kZeros && !((live >> j) & 1u)) a = b = 0u;
+        s[j] = v2f{__uint_as_float(a), __uint_as_float(b)};
+    }
+#pragma unroll
+    for (int jj = 0; jj < 5; jj++) {
+        v2f y = {0.0f, 0.0f};
+#pragma unroll
+        for (int j = 0; j < 10; j++) {
+            const int i = 48 - jj - 5 * (9 - j);
+            if (i < 0) continue;
+            y = __builtin_elementwise_fma(s[j], v2f{QK_RRC[i], QK_RRC[i]}, y);
+        }
+        y = y * QK_GAIN;
+        const float sr = y.x * ph[jj].x - y.y * ph[jj].y;   // crealf(signal * phase), src/qpsk.c:301-304
+        dst[jj] = (int16_t)(int)(sr * scale);               // src/qpsk.c:313-319
+    }
+}
+
+// grid.x = 8 * channel groups (class = x & 7), grid.y = tiles of this launch
+__global__ void __launch_bounds__(kThreads)
+tx_batch_kernel(const uint8_t* __restrict__ bits, const uint32_t* __restrict__ state,
+                const float2* __restrict__ tab, int16_t* __restrict__ out, long ld, int nch,
+                int npk, int gap, int first, long tile0) {
+    __shared__ __attribute__((aligned(16))) int16_t tile[2][kTile + 2 * kMargin];
+    __shared__ uint32_t sgn[kLoop][2][kSignWords];
+    const int tid = threadIdx.x;
+    const int cls = blockIdx.x & (kClasses - 1);
+    const long cbase = cls + (long)kClasses * kLoop * (blockIdx.x / kClasses);
+    if (cbase >= nch) return;
+    const int nloop = (int)lmin((long)kLoop, (nch - cbase + kClasses - 1) / kClasses);
+    const long P = (long)kTxPacket + gap;
+    const long N = (long)npk * P;
+    // samples from the row's start back to a 16-byte boundary: one value per class
+    const unsigned a = (unsigned)(((uintptr_t)out >> 1) + (uint64_t)cbase * (uint64_t)ld) & (kChunk - 1);
+    const long pl0 = (tile0 + blockIdx.y) * kTile - (long)a;   // the tile is [pl0, pl0 + kTile)
+    const long pl = pl0 > 0 ? pl0 : 0, pe = lmin(pl0 + kTile, N);
+    if (pl >= pe) return;
+    // TX samples of the call at positions < p; the tile holds [tlo, thi)
+    const long kl = pl / P, ke = pe / P;
+    const long tlo = kl * kTxPacket + lmin(pl - kl * P, (long)kTxPacket);
+    const long thi = ke * kTxPacket + lmin(pe - ke * P, (long)kTxPacket);
+    const long slo = tlo / 5;                                  // first period of the tile
+    const int nper = thi > tlo ? (int)((thi + 4) / 5 - slo) : 0;
+    const long k0 = slo / kSymPacket;
+    const int u0 = (int)(slo - k0 * kSymPacket);
+
+    // gap positions stay zero for every channel: nothing writes them again
+    for (int i = tid; i < (int)(sizeof(tile) / sizeof(uint32_t)); i += kThreads)
+        reinterpret_cast<uint32_t*>(&tile[0][0])[i] = 0u;
+    for (int i = tid; i < (int)(sizeof(sgn) / sizeof(uint32_t)); i += kThreads)
+        (&sgn[0][0][0])[i] = 0u;
+    __syncthreads();
+    // sign bits: bit b of a channel's strings is symbol slo - 9 + b of the call.
+    // A wave takes 64 symbols of one channel at a time (lane = symbol, so the
+    // payload bytes are read once, side by side) and ballots them into two
+    // words per component; kFetch of those are in flight together.
+    const int ngrp = (nper + kHist + 63) >> 6;
+    const int nitem = nloop * ngrp;
+    auto fetch = [&](int item, bool& neg_i, bool& neg_q) {
+        neg_i = neg_q = false;
+        if (item >= nitem) return;
+        const int i = item / ngrp, b = (item - i * ngrp) * 64 + (tid & 63);
+        if (b >= nper + kHist) return;
+        const long c = cbase + (long)kClasses * i;
+        const int rel = u0 - kHist + b;                // symbol of packet k0, or its neighbours
+        if (rel < 0 && k0 == 0) {                      // before this call: the saved 9 dibits
+            if (!first) {
+                const uint32_t st = state[c];
+                neg_i = (st >> (rel + kHist)) & 1u;
+                neg_q = (st >> (rel + kHist + 16)) & 1u;
+            }
+            return;
+        }
+        const int dk = rel < 0 ? -1 : rel / kSymPacket;
+        const int u = rel - dk * kSymPacket;
+        if (u < QK_NPRE) {
+            constexpr unsigned long long lo = pre_neg(0), hi = pre_neg(1);
+            neg_i = neg_q = ((u < 64 ? lo : hi) >> (u & 63)) & 1ull;
+        } else {   // bits[2s] = Q, bits[2s+1] = I; 62 = 2*31, so data symbol d is bytes 2d, 2d+1
+            const uint8_t* p = bits + ((size_t)c * npk + (size_t)(k0 + dk)) * kPacketBits +
+                               2 * (u - QK_NPRE);
+            neg_q = p[0] == 1;                         // qpsk_mod's `== 1`, src/qpsk.c:252-253
+            neg_i = p[1] == 1;
+        }
+    };
+    constexpr int kWaves = kThreads / 64, kFetch = 4;
+    for (int it = tid >> 6; it < nitem; it += kWaves * kFetch) {
+        bool ni[kFetch], nq[kFetch];
+#pragma unroll
+        for (int f = 0; f < kFetch; f++) fetch(it + f * kWaves, ni[f], nq[f]);
+#pragma unroll
+        for (int f = 0; f < kFetch; f++) {
+            const int item = it + f * kWaves;
+            const unsigned long long mi = __ballot(ni[f]), mq = __ballot(nq[f]);
+            if ((tid & 63) == 0 && item < nitem) {
+                const int i = item / ngrp, w = (item - i * ngrp) * 2;
+                sgn[i][0][w] = (uint32_t)mi;
+                sgn[i][0][w + 1] = (uint32_t)(mi >> 32);
+                sgn[i][1][w] = (uint32_t)mq;
+                sgn[i][1][w + 1] = (uint32_t)(mq >> 32);
+            }
+        }
+    }
+
+    // per period, independent of the channel
+    float2 ph[kRounds][5];
+    float scale[kRounds];
+    int slot[kRounds];
+    uint32_t live[kRounds];
+#pragma unroll
+    for (int rd = 0; rd < kRounds; rd++) {
+        const int n = tid + rd * kThreads;
+        scale[rd] = 0.0f;
+        slot[rd] = 0;
+        live[rd] = 0x3ffu;
+#pragma unroll
+        for (int jj = 0; jj < 5; jj++) ph[rd][jj] = make_float2(0.0f, 0.0f);
+        if (n < nper) {
+            const int rel = u0 + n;
+            const int dk = rel / kSymPacket;
+            const int u = rel - dk * kSymPacket;
+            const long p = (k0 + dk) * P + 5 * u;
+            slot[rd] = (int)(p - pl0) + kMargin;       // in [kMargin - 4, kMargin + kTile)
+            scale[rd] = u < QK_NPRE ? 8192.0f : 16384.0f;
+            const long S = slo + n;
+            if (first && S < kHist) live[rd] = 0x3ffu & (0x3ffu << (kHist - (int)S));
+#pragma unroll
+            for (int jj = 0; jj < 5; jj++) ph[rd][jj] = tab[5 * S + jj];
+        }
+    }
+    const bool zeros = first && slo < kHist;           // block-uniform: the stream's first 45 samples
+    const long p0 = pl0 + (long)tid * kChunk;          // this lane's 8 samples in the store pass
+    const bool whole = p0 >= 0 && p0 + kChunk <= N;
+    __syncthreads();
+
+    for (int i = 0; i < nloop; i++) {
+        int16_t* buf = tile[i & 1];
+#pragma unroll
+        for (int rd = 0; rd < kRounds; rd++) {
+            const int n = tid + rd * kThreads;
+            if (n >= nper) continue;
+            const uint32_t* wi = sgn[i][0];
+            const uint32_t* wq = sgn[i][1];
+            const uint32_t bi = __funnelshift_r(wi[n >> 5], wi[(n >> 5) + 1], n & 31);
+            const uint32_t bq = __funnelshift_r(wq[n >> 5], wq[(n >> 5) + 1], n & 31);
+            if (zeros) period<true>(bi, bq, live[rd], ph[rd], scale[rd], buf + slot[rd]);
+            else period<false>(bi, bq, 0x3ffu, ph[rd], scale[rd], buf + slot[rd]);
+        }
+        __syncthreads();   // one barrier per channel: the other buffer's readers passed the last one
+        int16_t* row = out + (size_t)(cbase + (long)kClasses * i) * (size_t)ld;
+        const int16_t* src = buf + kMargin + tid * kChunk;
+        if (whole) {
+            *reinterpret_cast<uint4*>(row + p0) = *reinterpret_cast<const uint4*>(src);
+        } else {
+            for (int e = 0; e < kChunk; e++)
+                if (p0 + e >= 0 && p0 + e < N) row[p0 + e] = src[e];
+        }
+    }
+}
+
+// The 9 dibits the next call's first packet filters over: data symbols
+// 239..247 of this call's last packet.  Bit j = I sign, bit 16 + j = Q sign.
+__global__ void __launch_bounds__(kThreads)
+tx_state_kernel(const uint8_t* __restrict__ bits, uint32_t* __restrict__ state, int nch, int npk) {
+    const long c = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (c >= nch) return;
+    const uint8_t* p = bits + ((size_t)c * npk + (size_t)(npk - 1)) * kPacketBits +
+                       2 * (kSymPacket - QK_NPRE - kHist);
+    uint32_t st = 0;
+    for (int j = 0; j < kHist; j++) {
+        st |= (uint32_t)(p[2 * j + 1] == 1) << j;
+        st |= (uint32_t)(p[2 * j] == 1) << (16 + j);
+    }
+    state[c] = st;
+}
+
+int herr(hipError_t e) { return e == hipSuccess ? QPSK_OK : QPSK_EHIP - (int)e; }
+#define HCHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return herr(e_); } while (0)
+
+}  // namespace
+
+struct qpsk_tx_ctx {
+    int device = 0, nch = 0, gap = 0;
+    uint64_t packets = 0;
+    float phase[2] = {1.0f, 0.0f};    // fbb_tx_phase before the next packet
+    uint32_t* d_state = nullptr;      // [nch] last 9 dibits sent
+    float2* d_tab = nullptr;          // carrier of the current call's TX samples
+    long tab_cap = 0;
+    // pinned staging of the carrier table: two slots, so a call never waits for
+    // the previous call's kernel before it builds its own table
+    float* h_stage[2] = {nullptr, nullptr};
+    long stage_cap[2] = {0, 0};
+    hipEvent_t ev_stage[2] = {nullptr, nullptr};   // the slot's upload has been read
+    int slot = 0;
+    hipEvent_t ev_last = nullptr;     // after the latest call's kernels
+    hipStream_t stream = nullptr;     // qpsk_tx_batch's own
+};
+
+extern "C" qpsk_tx_ctx* qpsk_tx_create(int device, int nch, int gap, int* err) {
+    int dummy;
+    if (!err) err = &dummy;
+    if (nch < 1 || gap < 0) {
+        *err = QPSK_EINVAL;
+        return nullptr;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        *err = QPSK_ENODEV;
+        return nullptr;
+    }
+    qpsk_tx_ctx* c = new (std::nothrow) qpsk_tx_ctx();
+    if (!c) {
+        *err = QPSK_ENOMEM;
+        return nullptr;
+    }
+    c->device = device;
+    c->nch = nch;
+    c->gap = gap;
+    int r = herr(hipSetDevice(device));
+    if (r == QPSK_OK) r = herr(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    if (r == QPSK_OK) r = herr(hipMalloc((void**)&c->d_state, sizeof(uint32_t) * (size_t)nch));
+    if (r == QPSK_OK) r = herr(hipMemset(c->d_state, 0, sizeof(uint32_t) * (size_t)nch));
+    for (int s = 0; s < 2 && r == QPSK_OK; s++)
+        r = herr(hipEventCreateWithFlags(&c->ev_stage[s], hipEventDisableTiming));
+    if (r == QPSK_OK) r = herr(hipEventCreateWithFlags(&c->ev_last, hipEventDisableTiming));
+    if (r != QPSK_OK) {
+        qpsk_tx_destroy(c);
+        *err = r == QPSK_EHIP - (int)hipErrorOutOfMemory ? QPSK_ENOMEM : r;
+        return nullptr;
+    }
+    *err = QPSK_OK;
+    return c;
+}
+
+extern "C" void qpsk_tx_destroy(qpsk_tx_ctx* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    if (c->ev_last) (void)hipEventSynchronize(c->ev_last);
+    for (int s = 0; s < 2; s++) {
+        if (c->ev_stage[s]) {
+            (void)hipEventSynchronize(c->ev_stage[s]);
+            (void)hipEventDestroy(c->ev_stage[s]);
+        }
+        if (c->h_stage[s]) (void)hipHostFree(c->h_stage[s]);
+    }
+    if (c->ev_last) (void)hipEventDestroy(c->ev_last);
+    if (c->d_tab) (void)hipFree(c->d_tab);
+    if (c->d_state) (void)hipFree(c->d_state);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
+}
+
+extern "C" int qpsk_tx_sync(qpsk_tx_ctx* c) {
+    if (!c) return QPSK_EINVAL;
+    HCHECK(hipSetDevice(c->device));
+    HCHECK(hipEventSynchronize(c->ev_last));
+    return QPSK_OK;
+}
+
+extern "C" int qpsk_tx_reset(qpsk_tx_ctx* c) {
+    const int r = qpsk_tx_sync(c);
+    if (r != QPSK_OK) return r;
+    c->packets = 0;   // the saved dibits are not read before the first packet
+    c->phase[0] = 1.0f;
+    c->phase[1] = 0.0f;
+    return QPSK_OK;
+}
+
+extern "C" int qpsk_tx_channels(const qpsk_tx_ctx* c) { return c ? c->nch : QPSK_EINVAL; }
+extern "C" int qpsk_tx_gap(const qpsk_tx_ctx* c) { return c ? c->gap : QPSK_EINVAL; }
+extern "C" uint64_t qpsk_tx_packets(const qpsk_tx_ctx* c) { return c ? c->packets : 0; }
+
+static int tx_check(const qpsk_tx_ctx* c, const void* bits, int npackets, const void* out, long ld) {
+    if (!c || npackets < 0) return QPSK_EINVAL;
+    if (npackets == 0) return QPSK_OK;
+    if (!bits || !out || (long)c->nch * npackets >= (1L << 28) ||
+        ld < (long)npackets * ((long)kTxPacket + c->gap))
+        return QPSK_EINVAL;
+    return QPSK_OK;
+}
+
+extern "C" int qpsk_tx_batch_device(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets,
+                                    int16_t* d_out, long ld, void* stream) {
+    const int chk = tx_check(c, d_bits, npackets, d_out, ld);
+    if (chk != QPSK_OK || npackets == 0) return chk;
+    hipStream_t s = (hipStream_t)stream;
+    HCHECK(hipSetDevice(c->device));
+    const long ntx = (long)npackets * kTxPacket;
+    if (ntx > c->tab_cap) {   // hipFree waits for the kernels that read the old table
+        if (c->d_tab) HCHECK(hipFree(c->d_tab));
+        c->d_tab = nullptr;
+        c->tab_cap = 0;
+        HCHECK(hipMalloc((void**)&c->d_tab, sizeof(float2) * (size_t)ntx));
+        c->tab_cap = ntx;
+    }
+    const int sl = c->slot;
+    HCHECK(hipEventSynchronize(c->ev_stage[sl]));   // the slot's previous upload (two calls ago)
+    if (ntx > c->stage_cap[sl]) {
+        if (c->h_stage[sl]) HCHECK(hipHostFree(c->h_stage[sl]));
+        c->h_stage[sl] = nullptr;
+        c->stage_cap[sl] = 0;
+        HCHECK(hipHostMalloc((void**)&c->h_stage[sl], sizeof(float) * 2 * (size_t)ntx, hipHostMallocDefault));
+        c->stage_cap[sl] = ntx;
+    }
+    // the carrier of this call's packets, continued from the carried phase; the
+    // context takes the new phase only once everything is enqueued
+    float ph[2] = {c->phase[0], c->phase[1]};
+    qpsk_tx_phase_run(c->h_stage[sl], ntx, ph);
+    HCHECK(hipMemcpyAsync(c->d_tab, c->h_stage[sl], sizeof(float2) * (size_t)ntx, hipMemcpyHostToDevice, s));
+    HCHECK(hipEventRecord(c->ev_stage[sl], s));
+    c->slot = sl ^ 1;
+    const long N = (long)npackets * ((long)kTxPacket + c->gap);
+    const long ntile = (N + (kChunk - 1) + kTile - 1) / kTile;   // the class with the longest head
+    const unsigned gx = (unsigned)(kClasses * (((long)c->nch + kClasses * kLoop - 1) / (kClasses * kLoop)));
+    const int first = c->packets == 0;
+    for (long t0 = 0; t0 < ntile; t0 += 65535) {
+        const unsigned gy = (unsigned)lmin(65535L, ntile - t0);
+        hipLaunchKernelGGL(tx_batch_kernel, dim3(gx, gy), dim3(kThreads), 0, s, d_bits, c->d_state,
+                           (const float2*)c->d_tab, d_out, ld, c->nch, npackets, c->gap, first, t0);
+        HCHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(tx_state_kernel, dim3((unsigned)((c->nch + kThreads - 1) / kThreads)),
+                       dim3(kThreads), 0, s, d_bits, c->d_state, c->nch, npackets);
+    HCHECK(hipGetLastError());
+    HCHECK(hipEventRecord(c->ev_last, s));
+    c->phase[0] = ph[0];
+    c->phase[1] = ph[1];
+    c->packets += (uint64_t)npackets;
+    return QPSK_OK;
+}
+
+extern "C" int qpsk_tx_batch(qpsk_tx_ctx* c, const uint8_t* bits, int npackets, int16_t* out, long ld) {
+    const int chk = tx_check(c, bits, npackets, out, ld);
+    if (chk != QPSK_OK || npackets == 0) return chk;
+    HCHECK(hipSetDevice(c->device));
+    const size_t nbits = (size_t)c->nch * (size_t)npackets * kPacketBits;
+    const size_t N = (size_t)npackets * (size_t)(kTxPacket + (long)c->gap);
+    uint8_t* d_bits = nullptr;
+    int16_t* d_out = nullptr;
+    int r = herr(hipMalloc((void**)&d_bits, nbits));
+    if (r == QPSK_OK) r = herr(hipMalloc((void**)&d_out, sizeof(int16_t) * N * (size_t)c->nch));
+    if (r == QPSK_OK) r = herr(hipMemcpyAsync(d_bits, bits, nbits, hipMemcpyHostToDevice, c->stream));
+    if (r == QPSK_OK) r = qpsk_tx_batch_device(c, d_bits, npackets, d_out, (long)N, c->stream);
+    // only the written samples come back: out[c][N .. ld) keeps its contents
+    if (r == QPSK_OK)
+        r = herr(hipMemcpy2DAsync(out, sizeof(int16_t) * (size_t)ld, d_out, sizeof(int16_t) * N,
+                                  sizeof(int16_t) * N, (size_t)c->nch, hipMemcpyDeviceToHost, c->stream));
+    const int r2 = herr(hipStreamSynchronize(c->stream));
+    if (r == QPSK_OK) r = r2;
+    if (d_bits) (void)hipFree(d_bits);
+    if (d_out) (void)hipFree(d_out);
+    if (r == QPSK_EHIP - (int)hipErrorOutOfMemory) r = QPSK_ENOMEM;
+    return r;
+}
