@@ -6,10 +6,10 @@
 set -eu
 cd "$(dirname "$0")"
 H=/opt/rocm/bin/hipcc
-B=../../singlecarrier_amd/csrc/build
-make -s -C ../../singlecarrier_amd/csrc >/dev/null
 F="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-gpu-flush-denormals-to-zero \
  -I../../include -I../../singlecarrier_amd/csrc -mllvm -amdgpu-sched-strategy=iterative-ilp"
 $H --offload-arch=gfx950 -O2 -o simd_probe simd_probe.hip
 $H $F -c -o /tmp/fir_probe.o fir_probe.hip
-$H --offload-arch=gfx950 -o fir_probe /tmp/fir_probe.o $B/qpsk_fft_host.o $B/qpsk_fft.o $B/qpsk_stream.o -lm -lpthread
+# fir_probe.hip includes qpsk_rx.hip, the kernels' translation unit, which needs
+# no other object of the library
+$H --offload-arch=gfx950 -o fir_probe /tmp/fir_probe.o -lm -lpthread

@@ -35,6 +35,64 @@ def test_makefile_hashes_the_listed_sources():
     assert tuple(body.replace("\\\n", " ").split()) == sc.KERNEL_SOURCES
 
 
+def _kernel_unit_deps():
+    """What qpsk_rx.hip, the kernels' translation unit, includes of the project
+    (the compiler's own list): csrc-local names and include/ names."""
+    import subprocess
+    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+    inc = os.path.abspath(os.path.join(os.path.dirname(CSRC), "..", "include"))
+    r = subprocess.run([hipcc, "--cuda-host-only", "-MM", "-std=c++17", f"-I{inc}", f"-I{CSRC}",
+                        os.path.join(CSRC, "qpsk_rx.hip")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    deps = [os.path.abspath(d) for d in r.stdout.split(":", 1)[1].replace("\\\n", " ").split()]
+    local = {os.path.basename(d) for d in deps if os.path.dirname(d) == os.path.abspath(CSRC)}
+    api = {os.path.basename(d) for d in deps if os.path.dirname(d) == inc}
+    assert len(local) + len(api) == len(deps), deps
+    return local, api
+
+
+def _mk_list(name):
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    body = re.search(rf"^{name}\s*:=((?:.*\\\n)*.*)$", mk, re.M).group(1)
+    return body.replace("\\\n", " ").split()
+
+
+def test_the_hash_covers_what_the_kernel_unit_includes_and_no_host_code():
+    """KSRC / KHDR are exactly the files the kernels' translation unit is made
+    from (plus the Makefile's own rules); the host side of the receive path
+    (qpsk_rx_host.*) is none of them, so a host edit keeps the counter records."""
+    local, api = _kernel_unit_deps()
+    ksrc, khdr = _mk_list("KSRC"), _mk_list("KHDR")
+    assert len(set(ksrc)) == len(ksrc) and set(ksrc) == local | {"Makefile"}
+    assert len(set(khdr)) == len(khdr) and all(h.startswith("$(INCDIR)/") for h in khdr)
+    assert {h[len("$(INCDIR)/"):] for h in khdr} == api
+    host = [f for f in os.listdir(CSRC) if f.startswith("qpsk_rx_host.")]
+    assert host and not any(f in local or f in ksrc for f in host)
+
+
+def test_a_host_file_byte_keeps_the_hash(tmp_path):
+    cur = sc.kernel_source_hash()
+    src = tmp_path / "csrc"
+    shutil.copytree(CSRC, src, ignore=shutil.ignore_patterns("build"))
+    assert sc.kernel_source_hash(str(src)) == cur
+    for f in src.glob("qpsk_rx_host.*"):
+        b = bytearray(f.read_bytes())
+        b[len(b) // 2] ^= 1
+        f.write_bytes(bytes(b))
+    assert sc.kernel_source_hash(str(src)) == cur
+
+
+def test_a_host_edit_rebuilds_only_the_host_object():
+    """The host file as if just edited (make -W): its object is rebuilt, the
+    kernels' translation unit is not compiled."""
+    _lib_built()
+    assert "qpsk_rx" not in _make("-n").stdout
+    dry = _make("-n", "-W", "qpsk_rx_host.hip")
+    assert dry.returncode == 0, dry.stderr
+    assert "qpsk_rx_host.hip" in dry.stdout and "build/qpsk_rx_host.o" in dry.stdout
+    assert "qpsk_rx.hip" not in dry.stdout and "build/qpsk_rx.o " in dry.stdout   # linked, not compiled
+
+
 def _write_records(root, khash, nch=65536, nf=32):
     os.makedirs(os.path.join(root, "profiles"), exist_ok=True)
     json.dump({"channels": nch, "frames": nf, "hbm_bytes_per_launch": 123, "kernel_hash": khash,
@@ -46,7 +104,8 @@ def _write_records(root, khash, nch=65536, nf=32):
 def test_one_flipped_source_byte_drops_the_counters(tmp_path):
     """Records profiled with the current kernels are reported; after one byte
     of qpsk_rx.hip changes, the rebuilt library's hash differs and both
-    records are dropped (traffic null, no measured valu)."""
+    records are dropped (traffic null, no measured valu).  So does one byte of
+    a header the kernels moved to."""
     cur = sc.kernel_source_hash()
     _write_records(str(tmp_path), cur)
     p = bench.pmc_record("pmc_traffic.json", 65536, 32, "reference", cur, root=str(tmp_path))
@@ -65,6 +124,15 @@ def test_one_flipped_source_byte_drops_the_counters(tmp_path):
     assert new != cur
     for name in ("pmc_traffic.json", "pmc_valu.json"):
         assert bench.pmc_record(name, 65536, 32, "reference", new, root=str(tmp_path)) is None
+    b[len(b) // 2] ^= 1   # back as it was
+    f.write_bytes(bytes(b))
+    assert sc.kernel_source_hash(str(src)) == cur
+    f = src / "qpsk_rx_back.h"
+    b = bytearray(f.read_bytes())
+    b[len(b) // 2] ^= 1
+    f.write_bytes(bytes(b))
+    moved = sc.kernel_source_hash(str(src))
+    assert moved != cur and moved != new
     assert bench.valu_from_counters(None, 6e-3) is None
     # a record without a hash (older profiles) is never reported either
     _write_records(str(tmp_path), None)
