@@ -11,6 +11,7 @@
 
 #include "qpsk_batch.h"
 #include "qpsk_consts.h"
+#include "qpsk_herr.h"   // herr, HCHECK
 
 // A workgroup owns G groups of 64 channels: waves 0..G-1 are their back waves,
 // waves G.. are front waves, FP per group (rx_kernel<G, FP>).  Every shape has
@@ -116,6 +117,3 @@ struct RxLaunch {
 int qpsk_rx_launch_kernels(const RxLaunch& a);
 // Takes the error word d_err[0] into d_err[1] in one atomic exchange, on stream s
 int qpsk_rx_take_err(int* d_err, hipStream_t s);
-
-static inline int herr(hipError_t e) { return e == hipSuccess ? QPSK_OK : QPSK_EHIP - (int)e; }
-#define HCHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return herr(e_); } while (0)

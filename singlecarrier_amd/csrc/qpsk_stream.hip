@@ -3,12 +3,14 @@
 // overlap.  Host code only; the receive is qpsk_rx_batch_device().
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <new>
 #include <stdint.h>
 #include <string.h>
 
 #include "qpsk_batch.h"
 #include "qpsk_consts.h"
+#include "qpsk_hip_host.h"
 #include "qpsk_rx_internal.h"
 #include "qpsk_stream.h"
 
@@ -17,19 +19,15 @@ namespace {
 constexpr int kMaxSlots = 4;
 
 struct Slot {
-    int16_t* h_in = nullptr;     // pinned
-    int16_t* d_in = nullptr;
-    uint8_t* d_bits = nullptr;
-    uint8_t* d_valid = nullptr;
-    uint8_t* h_bits = nullptr;   // pinned
-    uint8_t* h_valid = nullptr;  // pinned
-    int* d_err = nullptr;        // the chunk's device error word (progress-wait stalls)
-    int* h_err = nullptr;        // pinned copy, read by qpsk_stream_retrieve
-    hipEvent_t copied = nullptr, received = nullptr, done = nullptr;
+    qhip::PinBuf<int16_t> h_in;
+    qhip::DevBuf<int16_t> d_in;
+    qhip::DevBuf<uint8_t> d_bits, d_valid;
+    qhip::PinBuf<uint8_t> h_bits, h_valid;
+    qhip::DevBuf<int> d_err;     // the chunk's device error word (progress-wait stalls)
+    qhip::PinBuf<int> h_err;     // pinned copy, read by qpsk_stream_retrieve
+    qhip::Event copied, received, done;
     uint64_t epoch = 0;          // qpsk_rx_epoch() when the chunk was submitted
 };
-
-int herr(hipError_t e) { return e == hipSuccess ? QPSK_OK : QPSK_EHIP - (int)e; }
 
 // a slot's stall also goes into the context's own error word (qpsk_rx_sync)
 __global__ void err_merge_kernel(int* ctx_err, const int* slot_err) {
@@ -40,8 +38,12 @@ __global__ void err_merge_kernel(int* ctx_err, const int* slot_err) {
 
 struct qpsk_stream {
     int device = 0, nch = 0, frames = 0, nslot = 0;
-    qpsk_ctx* rx = nullptr;
-    hipStream_t s_h2d = nullptr, s_rx = nullptr, s_d2h = nullptr;
+    // released in reverse order: the slots, the streams, then the receiver
+    struct RxDestroy {
+        void operator()(qpsk_ctx* c) const { qpsk_rx_destroy(c); }
+    };
+    std::unique_ptr<qpsk_ctx, RxDestroy> rx;
+    qhip::Stream s_h2d, s_rx, s_d2h;
     Slot slot[kMaxSlots];
     uint64_t acquired = 0, submitted = 0, retrieved = 0;
     // A stalled chunk leaves every channel's carried state (rx_timing, windows,
@@ -53,49 +55,25 @@ struct qpsk_stream {
     uint64_t stall_epoch = 0;
 };
 
-#define SCHECK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return herr(e_); } while (0)
-
-static void stream_free(qpsk_stream* s) {
-    (void)hipSetDevice(s->device);
-    for (int i = 0; i < s->nslot; i++) {
-        Slot& q = s->slot[i];
-        (void)hipHostFree(q.h_in);
-        (void)hipHostFree(q.h_bits);
-        (void)hipHostFree(q.h_valid);
-        (void)hipHostFree(q.h_err);
-        (void)hipFree(q.d_err);
-        (void)hipFree(q.d_in);
-        (void)hipFree(q.d_bits);
-        (void)hipFree(q.d_valid);
-        if (q.copied) (void)hipEventDestroy(q.copied);
-        if (q.received) (void)hipEventDestroy(q.received);
-        if (q.done) (void)hipEventDestroy(q.done);
-    }
-    if (s->s_h2d) (void)hipStreamDestroy(s->s_h2d);
-    if (s->s_rx) (void)hipStreamDestroy(s->s_rx);
-    if (s->s_d2h) (void)hipStreamDestroy(s->s_d2h);
-    if (s->rx) qpsk_rx_destroy(s->rx);
-}
-
 static int stream_alloc(qpsk_stream* s) {
-    SCHECK(hipSetDevice(s->device));
-    SCHECK(hipStreamCreateWithFlags(&s->s_h2d, hipStreamNonBlocking));
-    SCHECK(hipStreamCreateWithFlags(&s->s_rx, hipStreamNonBlocking));
-    SCHECK(hipStreamCreateWithFlags(&s->s_d2h, hipStreamNonBlocking));
+    HCHECK(hipSetDevice(s->device));
+    HCHECK(s->s_h2d.create());
+    HCHECK(s->s_rx.create());
+    HCHECK(s->s_d2h.create());
     const size_t cf = (size_t)s->nch * (size_t)s->frames;
     for (int i = 0; i < s->nslot; i++) {
         Slot& q = s->slot[i];
-        SCHECK(hipHostMalloc((void**)&q.h_in, sizeof(int16_t) * cf * QK_FRAME, hipHostMallocDefault));
-        SCHECK(hipHostMalloc((void**)&q.h_bits, cf * QK_NBITS, hipHostMallocDefault));
-        SCHECK(hipHostMalloc((void**)&q.h_valid, cf, hipHostMallocDefault));
-        SCHECK(hipMalloc((void**)&q.d_in, sizeof(int16_t) * cf * QK_FRAME));
-        SCHECK(hipMalloc((void**)&q.d_bits, cf * QK_NBITS));
-        SCHECK(hipMalloc((void**)&q.d_valid, cf));
-        SCHECK(hipMalloc((void**)&q.d_err, sizeof(int)));
-        SCHECK(hipHostMalloc((void**)&q.h_err, sizeof(int), hipHostMallocDefault));
-        SCHECK(hipEventCreateWithFlags(&q.copied, hipEventDisableTiming));
-        SCHECK(hipEventCreateWithFlags(&q.received, hipEventDisableTiming));
-        SCHECK(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+        HCHECK(q.h_in.reserve(cf * QK_FRAME));
+        HCHECK(q.h_bits.reserve(cf * QK_NBITS));
+        HCHECK(q.h_valid.reserve(cf));
+        HCHECK(q.d_in.reserve(cf * QK_FRAME));
+        HCHECK(q.d_bits.reserve(cf * QK_NBITS));
+        HCHECK(q.d_valid.reserve(cf));
+        HCHECK(q.d_err.reserve(1));
+        HCHECK(q.h_err.reserve(1));
+        HCHECK(q.copied.create(hipEventDisableTiming));
+        HCHECK(q.received.create(hipEventDisableTiming));
+        HCHECK(q.done.create(hipEventDisableTiming));
     }
     return QPSK_OK;
 }
@@ -106,31 +84,24 @@ extern "C" qpsk_stream* qpsk_stream_create(int device, int nch, int frames, int 
 
 extern "C" qpsk_stream* qpsk_stream_create_mode(int device, int nch, int frames, int nslot,
                                                 int mode, int* err) {
-    int dummy;
-    if (!err) err = &dummy;
-    if (nch < 1 || frames < 1 || nslot < 1 || nslot > kMaxSlots) {
-        *err = QPSK_EINVAL;
-        return nullptr;
-    }
+    if (nch < 1 || frames < 1 || nslot < 1 || nslot > kMaxSlots) return qhip::fail(err, QPSK_EINVAL);
     qpsk_stream* s = new (std::nothrow) qpsk_stream();
-    if (!s) {
-        *err = QPSK_ENOMEM;
-        return nullptr;
-    }
+    if (!s) return qhip::fail(err, QPSK_ENOMEM);
     s->device = device;
     s->nch = nch;
     s->frames = frames;
     s->nslot = nslot;
-    s->rx = qpsk_rx_create_mode(device, nch, mode, err);
-    if (s->rx) qpsk_rx_set_owner(s->rx, s);
-    int r = s->rx ? stream_alloc(s) : *err;
-    if (r != QPSK_OK) {
-        stream_free(s);
-        delete s;
-        *err = r;
-        return nullptr;
+    int r = QPSK_OK;
+    s->rx.reset(qpsk_rx_create_mode(device, nch, mode, &r));
+    if (s->rx) {
+        qpsk_rx_set_owner(s->rx.get(), s);
+        r = stream_alloc(s);
     }
-    *err = QPSK_OK;
+    if (r != QPSK_OK) {
+        delete s;
+        return qhip::fail(err, r);
+    }
+    qhip::set_err(err, QPSK_OK);
     return s;
 }
 
@@ -140,28 +111,19 @@ extern "C" void qpsk_stream_destroy(qpsk_stream* s) {
     (void)hipStreamSynchronize(s->s_h2d);
     (void)hipStreamSynchronize(s->s_rx);
     (void)hipStreamSynchronize(s->s_d2h);
-    stream_free(s);
     delete s;
 }
 
 extern "C" int16_t* qpsk_stream_acquire(qpsk_stream* s, int* err) {
-    int dummy;
-    if (!err) err = &dummy;
-    if (!s) {
-        *err = QPSK_EINVAL;
-        return nullptr;
-    }
+    if (!s) return qhip::fail(err, QPSK_EINVAL);
     if (s->acquired != s->submitted) {   // acquired twice without a submit
-        *err = QPSK_OK;
+        qhip::set_err(err, QPSK_OK);
         return s->slot[s->acquired % (uint64_t)s->nslot].h_in;
     }
     // the slot's previous chunk must have been retrieved (its outputs and its
     // input buffer are the caller's until then)
-    if (s->acquired - s->retrieved >= (uint64_t)s->nslot) {
-        *err = QPSK_EBUSY;
-        return nullptr;
-    }
-    *err = QPSK_OK;
+    if (s->acquired - s->retrieved >= (uint64_t)s->nslot) return qhip::fail(err, QPSK_EBUSY);
+    qhip::set_err(err, QPSK_OK);
     return s->slot[s->acquired++ % (uint64_t)s->nslot].h_in;
 }
 
@@ -169,24 +131,24 @@ extern "C" int qpsk_stream_submit(qpsk_stream* s) {
     if (!s || s->submitted == s->acquired) return QPSK_EINVAL;
     Slot& q = s->slot[s->submitted % (uint64_t)s->nslot];
     const size_t cf = (size_t)s->nch * (size_t)s->frames;
-    SCHECK(hipSetDevice(s->device));
-    SCHECK(hipMemcpyAsync(q.d_in, q.h_in, sizeof(int16_t) * cf * QK_FRAME, hipMemcpyHostToDevice,
+    HCHECK(hipSetDevice(s->device));
+    HCHECK(hipMemcpyAsync(q.d_in, q.h_in, sizeof(int16_t) * cf * QK_FRAME, hipMemcpyHostToDevice,
                           s->s_h2d));
-    SCHECK(hipEventRecord(q.copied, s->s_h2d));
-    SCHECK(hipStreamWaitEvent(s->s_rx, q.copied, 0));
-    SCHECK(hipMemsetAsync(q.d_err, 0, sizeof(int), s->s_rx));
-    const int r = qpsk_rx_launch(s->rx, q.d_in, s->frames, q.d_bits, q.d_valid, nullptr, nullptr,
+    HCHECK(hipEventRecord(q.copied, s->s_h2d));
+    HCHECK(hipStreamWaitEvent(s->s_rx, q.copied, 0));
+    HCHECK(hipMemsetAsync(q.d_err, 0, sizeof(int), s->s_rx));
+    const int r = qpsk_rx_launch(s->rx.get(), q.d_in, s->frames, q.d_bits, q.d_valid, nullptr, nullptr,
                                  s->s_rx, q.d_err);
     if (r != QPSK_OK) return r;
-    hipLaunchKernelGGL(err_merge_kernel, dim3(1), dim3(64), 0, s->s_rx, qpsk_rx_err_word(s->rx), q.d_err);
-    SCHECK(hipGetLastError());
-    SCHECK(hipEventRecord(q.received, s->s_rx));
-    SCHECK(hipStreamWaitEvent(s->s_d2h, q.received, 0));
-    SCHECK(hipMemcpyAsync(q.h_bits, q.d_bits, cf * QK_NBITS, hipMemcpyDeviceToHost, s->s_d2h));
-    SCHECK(hipMemcpyAsync(q.h_valid, q.d_valid, cf, hipMemcpyDeviceToHost, s->s_d2h));
-    SCHECK(hipMemcpyAsync(q.h_err, q.d_err, sizeof(int), hipMemcpyDeviceToHost, s->s_d2h));
-    SCHECK(hipEventRecord(q.done, s->s_d2h));
-    q.epoch = qpsk_rx_epoch(s->rx);
+    hipLaunchKernelGGL(err_merge_kernel, dim3(1), dim3(64), 0, s->s_rx, qpsk_rx_err_word(s->rx.get()), q.d_err);
+    HCHECK(hipGetLastError());
+    HCHECK(hipEventRecord(q.received, s->s_rx));
+    HCHECK(hipStreamWaitEvent(s->s_d2h, q.received, 0));
+    HCHECK(hipMemcpyAsync(q.h_bits, q.d_bits, cf * QK_NBITS, hipMemcpyDeviceToHost, s->s_d2h));
+    HCHECK(hipMemcpyAsync(q.h_valid, q.d_valid, cf, hipMemcpyDeviceToHost, s->s_d2h));
+    HCHECK(hipMemcpyAsync(q.h_err, q.d_err, sizeof(int), hipMemcpyDeviceToHost, s->s_d2h));
+    HCHECK(hipEventRecord(q.done, s->s_d2h));
+    q.epoch = qpsk_rx_epoch(s->rx.get());
     s->submitted++;
     return QPSK_OK;
 }
@@ -198,8 +160,8 @@ extern "C" int qpsk_stream_pending(const qpsk_stream* s) {
 extern "C" int qpsk_stream_retrieve(qpsk_stream* s, const uint8_t** bits, const uint8_t** valid) {
     if (!s || !bits || !valid || s->retrieved == s->submitted) return QPSK_EINVAL;
     Slot& q = s->slot[s->retrieved % (uint64_t)s->nslot];
-    SCHECK(hipSetDevice(s->device));
-    SCHECK(hipEventSynchronize(q.done));
+    HCHECK(hipSetDevice(s->device));
+    HCHECK(hipEventSynchronize(q.done));
     *bits = q.h_bits;
     *valid = q.h_valid;
     s->retrieved++;
@@ -211,11 +173,11 @@ extern "C" int qpsk_stream_retrieve(qpsk_stream* s, const uint8_t** bits, const 
     if (*q.h_err != 0) {
         s->stalled = true;
         s->stall_epoch = q.epoch;
-        qpsk_rx_mark_stalled(s->rx, q.epoch);   // the context's state too (qpsk_rx_state_save)
+        qpsk_rx_mark_stalled(s->rx.get(), q.epoch);   // the context's state too (qpsk_rx_state_save)
     }
     return (s->stalled && q.epoch == s->stall_epoch) ? QPSK_ESTALL : QPSK_OK;
 }
 
-extern "C" qpsk_ctx* qpsk_stream_ctx(qpsk_stream* s) { return s ? s->rx : nullptr; }
+extern "C" qpsk_ctx* qpsk_stream_ctx(qpsk_stream* s) { return s ? s->rx.get() : nullptr; }
 
 // qpsk_records(): host C, qpsk_records.c

@@ -4,11 +4,10 @@
  * channels.
  */
 #include <math.h>
-#include <pthread.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include "qpsk_consts.h"
+#include "qpsk_fanout.h"
 #include "qpsk_synth.h"
 
 #define PACKET 2783          /* 640 + 8*155 + 903 samples */
@@ -64,32 +63,21 @@ static void synth_channel(uint64_t seed, uint32_t c, double ebn0_db, int16_t *ou
 typedef struct {
     uint64_t seed;
     uint32_t c0;
-    int lo, hi;
     double ebn0;
     int16_t *out;
     long ns;
 } job_t;
 
-static void *worker(void *arg) {
-    job_t *j = (job_t *)arg;
-    for (int c = j->lo; c < j->hi; c++)
+static void share(void *arg, int lo, int hi) {
+    const job_t *j = (const job_t *)arg;
+    for (int c = lo; c < hi; c++)
         synth_channel(j->seed, j->c0 + (uint32_t)c, j->ebn0, j->out + (size_t)c * j->ns, j->ns);
-    return NULL;
 }
 
 void qpsk_synth_batch(uint64_t seed, uint32_t c0, int nch, double ebn0_db, int16_t *out,
                       long nsamples, int nthreads) {
     if (nch < 1) return;
-    if (nthreads < 1) nthreads = 1;
-    if (nthreads > nch) nthreads = nch;
-    job_t *jobs = (job_t *)calloc((size_t)nthreads, sizeof(job_t));
-    pthread_t *th = (pthread_t *)calloc((size_t)nthreads, sizeof(pthread_t));
-    for (int t = 0; t < nthreads; t++) {
-        jobs[t] = (job_t){seed, c0, (int)((long)nch * t / nthreads),
-                          (int)((long)nch * (t + 1) / nthreads), ebn0_db, out, nsamples};
-        pthread_create(&th[t], NULL, worker, &jobs[t]);
-    }
-    for (int t = 0; t < nthreads; t++) pthread_join(th[t], NULL);
-    free(jobs);
-    free(th);
+    job_t job = {seed, c0, ebn0_db, out, nsamples};
+    /* no way to report a failed allocation: every channel in this thread then */
+    if (qpsk_fanout(nch, nthreads, share, &job) != 0) share(&job, 0, nch);
 }

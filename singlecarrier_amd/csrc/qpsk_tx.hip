@@ -43,6 +43,7 @@
 #include <string.h>
 
 #include "qpsk_consts.h"
+#include "qpsk_hip_host.h"
 #include "qpsk_tx.h"
 #include "qpsk_tx_internal.h"
 
@@ -275,8 +276,8 @@ tx_state_kernel(const uint8_t* __restrict__ bits, uint32_t* __restrict__ state, 
     state[c] = st;
 }
 
-int herr(hipError_t e) { return e == hipSuccess ? QPSK_OK : QPSK_EHIP - (int)e; }
-#define HCHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return herr(e_); } while (0)
+// an allocation the device refused is QPSK_ENOMEM to the transmitter's callers
+int enomem(int r) { return r == QPSK_EHIP - (int)hipErrorOutOfMemory ? QPSK_ENOMEM : r; }
 
 }  // namespace
 
@@ -284,52 +285,36 @@ struct qpsk_tx_ctx {
     int device = 0, nch = 0, gap = 0;
     uint64_t packets = 0;
     float phase[2] = {1.0f, 0.0f};    // fbb_tx_phase before the next packet
-    uint32_t* d_state = nullptr;      // [nch] last 9 dibits sent
-    float2* d_tab = nullptr;          // carrier of the current call's TX samples
-    long tab_cap = 0;
+    qhip::Stream stream;              // qpsk_tx_batch's own (first: released last)
+    qhip::DevBuf<uint32_t> d_state;   // [nch] last 9 dibits sent
+    qhip::DevBuf<float2> d_tab;       // carrier of the current call's TX samples
     // pinned staging of the carrier table: two slots, so a call never waits for
     // the previous call's kernel before it builds its own table
-    float* h_stage[2] = {nullptr, nullptr};
-    long stage_cap[2] = {0, 0};
-    hipEvent_t ev_stage[2] = {nullptr, nullptr};   // the slot's upload has been read
+    qhip::PinBuf<float> h_stage[2];      // (re, im) pairs
+    qhip::Event ev_stage[2];          // the slot's upload has been read
     int slot = 0;
-    hipEvent_t ev_last = nullptr;     // after the latest call's kernels
-    hipStream_t stream = nullptr;     // qpsk_tx_batch's own
+    qhip::Event ev_last;              // after the latest call's kernels
 };
 
 extern "C" qpsk_tx_ctx* qpsk_tx_create(int device, int nch, int gap, int* err) {
-    int dummy;
-    if (!err) err = &dummy;
-    if (nch < 1 || gap < 0) {
-        *err = QPSK_EINVAL;
-        return nullptr;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        *err = QPSK_ENODEV;
-        return nullptr;
-    }
+    if (nch < 1 || gap < 0) return qhip::fail(err, QPSK_EINVAL);
+    if (!qhip::device_ok(device)) return qhip::fail(err, QPSK_ENODEV);
     qpsk_tx_ctx* c = new (std::nothrow) qpsk_tx_ctx();
-    if (!c) {
-        *err = QPSK_ENOMEM;
-        return nullptr;
-    }
+    if (!c) return qhip::fail(err, QPSK_ENOMEM);
     c->device = device;
     c->nch = nch;
     c->gap = gap;
     int r = herr(hipSetDevice(device));
-    if (r == QPSK_OK) r = herr(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    if (r == QPSK_OK) r = herr(hipMalloc((void**)&c->d_state, sizeof(uint32_t) * (size_t)nch));
+    if (r == QPSK_OK) r = herr(c->stream.create());
+    if (r == QPSK_OK) r = herr(c->d_state.reserve((size_t)nch));
     if (r == QPSK_OK) r = herr(hipMemset(c->d_state, 0, sizeof(uint32_t) * (size_t)nch));
-    for (int s = 0; s < 2 && r == QPSK_OK; s++)
-        r = herr(hipEventCreateWithFlags(&c->ev_stage[s], hipEventDisableTiming));
-    if (r == QPSK_OK) r = herr(hipEventCreateWithFlags(&c->ev_last, hipEventDisableTiming));
+    for (int s = 0; s < 2 && r == QPSK_OK; s++) r = herr(c->ev_stage[s].create(hipEventDisableTiming));
+    if (r == QPSK_OK) r = herr(c->ev_last.create(hipEventDisableTiming));
     if (r != QPSK_OK) {
         qpsk_tx_destroy(c);
-        *err = r == QPSK_EHIP - (int)hipErrorOutOfMemory ? QPSK_ENOMEM : r;
-        return nullptr;
+        return qhip::fail(err, enomem(r));
     }
-    *err = QPSK_OK;
+    qhip::set_err(err, QPSK_OK);
     return c;
 }
 
@@ -337,17 +322,8 @@ extern "C" void qpsk_tx_destroy(qpsk_tx_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->ev_last) (void)hipEventSynchronize(c->ev_last);
-    for (int s = 0; s < 2; s++) {
-        if (c->ev_stage[s]) {
-            (void)hipEventSynchronize(c->ev_stage[s]);
-            (void)hipEventDestroy(c->ev_stage[s]);
-        }
-        if (c->h_stage[s]) (void)hipHostFree(c->h_stage[s]);
-    }
-    if (c->ev_last) (void)hipEventDestroy(c->ev_last);
-    if (c->d_tab) (void)hipFree(c->d_tab);
-    if (c->d_state) (void)hipFree(c->d_state);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    for (int s = 0; s < 2; s++)
+        if (c->ev_stage[s]) (void)hipEventSynchronize(c->ev_stage[s]);
     delete c;
 }
 
@@ -387,21 +363,15 @@ extern "C" int qpsk_tx_batch_device(qpsk_tx_ctx* c, const uint8_t* d_bits, int n
     hipStream_t s = (hipStream_t)stream;
     HCHECK(hipSetDevice(c->device));
     const long ntx = (long)npackets * kTxPacket;
-    if (ntx > c->tab_cap) {   // hipFree waits for the kernels that read the old table
-        if (c->d_tab) HCHECK(hipFree(c->d_tab));
-        c->d_tab = nullptr;
-        c->tab_cap = 0;
-        HCHECK(hipMalloc((void**)&c->d_tab, sizeof(float2) * (size_t)ntx));
-        c->tab_cap = ntx;
+    if ((size_t)ntx > c->d_tab.cap()) {   // the release waits for the kernels that read the old table
+        HCHECK(c->d_tab.release());
+        HCHECK(c->d_tab.reserve((size_t)ntx));
     }
     const int sl = c->slot;
     HCHECK(hipEventSynchronize(c->ev_stage[sl]));   // the slot's previous upload (two calls ago)
-    if (ntx > c->stage_cap[sl]) {
-        if (c->h_stage[sl]) HCHECK(hipHostFree(c->h_stage[sl]));
-        c->h_stage[sl] = nullptr;
-        c->stage_cap[sl] = 0;
-        HCHECK(hipHostMalloc((void**)&c->h_stage[sl], sizeof(float) * 2 * (size_t)ntx, hipHostMallocDefault));
-        c->stage_cap[sl] = ntx;
+    if (2 * (size_t)ntx > c->h_stage[sl].cap()) {
+        HCHECK(c->h_stage[sl].release());
+        HCHECK(c->h_stage[sl].reserve(2 * (size_t)ntx));
     }
     // the carrier of this call's packets, continued from the carried phase; the
     // context takes the new phase only once everything is enqueued
@@ -417,7 +387,7 @@ extern "C" int qpsk_tx_batch_device(qpsk_tx_ctx* c, const uint8_t* d_bits, int n
     for (long t0 = 0; t0 < ntile; t0 += 65535) {
         const unsigned gy = (unsigned)lmin(65535L, ntile - t0);
         hipLaunchKernelGGL(tx_batch_kernel, dim3(gx, gy), dim3(kThreads), 0, s, d_bits, c->d_state,
-                           (const float2*)c->d_tab, d_out, ld, c->nch, npackets, c->gap, first, t0);
+                           (const float2*)c->d_tab.get(), d_out, ld, c->nch, npackets, c->gap, first, t0);
         HCHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(tx_state_kernel, dim3((unsigned)((c->nch + kThreads - 1) / kThreads)),
@@ -436,10 +406,10 @@ extern "C" int qpsk_tx_batch(qpsk_tx_ctx* c, const uint8_t* bits, int npackets, 
     HCHECK(hipSetDevice(c->device));
     const size_t nbits = (size_t)c->nch * (size_t)npackets * kPacketBits;
     const size_t N = (size_t)npackets * (size_t)(kTxPacket + (long)c->gap);
-    uint8_t* d_bits = nullptr;
-    int16_t* d_out = nullptr;
-    int r = herr(hipMalloc((void**)&d_bits, nbits));
-    if (r == QPSK_OK) r = herr(hipMalloc((void**)&d_out, sizeof(int16_t) * N * (size_t)c->nch));
+    qhip::DevBuf<uint8_t> d_bits;   // released on return, after the synchronisation
+    qhip::DevBuf<int16_t> d_out;
+    int r = herr(d_bits.reserve(nbits));
+    if (r == QPSK_OK) r = herr(d_out.reserve(N * (size_t)c->nch));
     if (r == QPSK_OK) r = herr(hipMemcpyAsync(d_bits, bits, nbits, hipMemcpyHostToDevice, c->stream));
     if (r == QPSK_OK) r = qpsk_tx_batch_device(c, d_bits, npackets, d_out, (long)N, c->stream);
     // only the written samples come back: out[c][N .. ld) keeps its contents
@@ -448,8 +418,5 @@ extern "C" int qpsk_tx_batch(qpsk_tx_ctx* c, const uint8_t* bits, int npackets, 
                                   sizeof(int16_t) * N, (size_t)c->nch, hipMemcpyDeviceToHost, c->stream));
     const int r2 = herr(hipStreamSynchronize(c->stream));
     if (r == QPSK_OK) r = r2;
-    if (d_bits) (void)hipFree(d_bits);
-    if (d_out) (void)hipFree(d_out);
-    if (r == QPSK_EHIP - (int)hipErrorOutOfMemory) r = QPSK_ENOMEM;
-    return r;
+    return enomem(r);
 }

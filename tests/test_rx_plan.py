@@ -1,0 +1,48 @@
+"""The receive path's host decisions on the CPU (csrc/qpsk_rx_plan.h): which
+rx_kernel instantiation a batch gets (thresholds of DESIGN.md "Kernels" on a
+256-CU device, forced shape, width and priority), the layout of the
+host-memory entry point's staging block, and the snapshot size.  The header
+makes no HIP runtime call, so tests/sanitize/rx_plan_check.cc is built with
+plain g++ under ASan + UBSan and run here; any report or failed check fails
+the test.  CPU only."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "singlecarrier_amd", "csrc")
+SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
+
+
+@pytest.fixture(scope="module")
+def plan_out(tmp_path_factory):
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path_factory.mktemp("plan") / "rx_plan_check")
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", *SAN, "-D__HIP_PLATFORM_AMD__",
+                    "-I" + os.path.join(rocm, "include"), "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
+                    "-o", exe, os.path.join(ROOT, "tests", "sanitize", "rx_plan_check.cc")], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, f"rx_plan_check failed ({r.returncode}):\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    return r.stdout
+
+
+def test_shapes_and_staging_layout(plan_out):
+    """Every check of the stand-alone program held (it prints the ones that
+    did not and exits nonzero) and it ran to its end."""
+    assert "FAILED" not in plan_out
+    assert plan_out.count("state_size") == 5
+
+
+def test_state_size_matches_the_abi_formula(plan_out):
+    """rx_state_size, which qpsk_rx_state_size returns, against the formula of
+    tests/test_abi.py::test_state_snapshot_size."""
+    per = 2 * 1880 * 2 + 168 * 8 + 4 + 4
+    got = {int(l.split()[1]): int(l.split()[2]) for l in plan_out.splitlines() if l.startswith("state_size")}
+    assert got == {0: 0, -3: 0, 1: 64 + per, 96: 64 + 96 * per, 65536: 64 + 65536 * per}
