@@ -72,6 +72,8 @@ def cpu_lib():
         lib.qc_fft_hunt.argtypes = [C.c_void_p]
         lib.qc_fft_hunt_spectrum.argtypes = [C.c_void_p]
         lib.qc_keystream.argtypes = [C.c_void_p, C.c_int]
+        lib.qc_cmul.restype = None
+        lib.qc_cmul.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]
         _cpu = lib
     return _cpu
 
@@ -233,6 +235,17 @@ def keystream(n: int) -> np.ndarray:
     ks = np.zeros(n, np.uint8)
     cpu_lib().qc_keystream(_p(ks), n)
     return ks
+
+
+def cmul(ops) -> np.ndarray:
+    """qc_cmul over ops [n][4] = (a, b, c, d): (a + bi)(c + di) as the
+    reference's gcc build computes a complex float product -> [n][2]."""
+    ops = np.ascontiguousarray(ops, np.float32).reshape(-1, 4)
+    out = np.empty((ops.shape[0], 2), np.float32)
+    f = cpu_lib().qc_cmul
+    for i, (a, b, c, d) in enumerate(ops.tolist()):
+        f(a, b, c, d, _p(out[i]))
+    return out
 
 
 def preamble() -> np.ndarray:

@@ -4,8 +4,12 @@
  *
  * Arithmetic contract: IEEE fp32, round-to-nearest, every
  * product and sum rounded separately (built with -ffp-contract=off), sums in
- * the reference's index order starting from 0.0f, complex products written out
- * as (ac - bd, ad + bc) exactly as gcc expands them for finite operands.
+ * the reference's index order starting from 0.0f.  A complex product of the
+ * receive path is cmul() below: (ac - bd, ad + bc) first, as gcc inlines it,
+ * and, when both parts come out NaN, the C99 Annex G recovery gcc then calls
+ * (the equalizer state leaves fp32 range on ordinary int16 input such as
+ * full-scale tones, and valid frames carry inf/NaN soft symbols there).
+ * Complex-by-real products are componentwise, as gcc expands them.
  *
  * Minimal form, each step proved equal to the reference:
  *  - mixer: frame n uses (-1)^n * P[t] (A.2), P[t] = R^(t+1) by the fp32
@@ -28,6 +32,7 @@
  */
 #include "cpu_ref.h"
 
+#include <complex.h>
 #include <math.h>
 #include <pthread.h>
 #include <stdlib.h>
@@ -146,6 +151,45 @@ static inline void fir_at(const float (*M)[2], float out[2]) {
     out[1] = yi * GAIN_F;
 }
 
+/* ---- complex product with gcc's semantics ----------------------------------
+ * (a + bi)(c + di) as gcc -O2 compiles a C99 `complex float` product without
+ * -ffast-math: the four products and (ac - bd, ad + bc) inline; only if BOTH
+ * parts are NaN, the out-of-line Annex G routine, which turns the NaNs of
+ * inf * 0 and inf - inf back into infinities (G.5.1).  The slow path is the
+ * compiler's own _Complex multiply on the same operands, so it is that routine
+ * by construction.  qc_naive_cmul (test switch, cpu_ref.h) leaves the NaNs. */
+int qc_naive_cmul;
+
+/* Diagnostics for the GPU's fast-path test (cpu_ref.h qc_unflagged_segments):
+ * per thread, did a product of the current segment (a frame's 128 training
+ * steps, or its 31 data steps) have both inline parts NaN, and did a divisor
+ * operand a_4 + ht leave (0, 2^125]. */
+static _Thread_local int t_both_nan, t_div_range;
+long qc_unflagged_segments, qc_flagged_segments;
+int qc_count_segments;
+
+static __attribute__((noinline)) void cmul_annex_g(float a, float b, float c, float d,
+                                                   float *re, float *im) {
+    const float complex p = CMPLXF(a, b) * CMPLXF(c, d);
+    *re = crealf(p);
+    *im = cimagf(p);
+}
+
+static inline void cmul(float a, float b, float c, float d, float *re, float *im) {
+    float x = a * c - b * d;
+    float y = a * d + b * c;
+    if (__builtin_expect(x != x && y != y, 0)) {
+        t_both_nan = 1;
+        if (!qc_naive_cmul) cmul_annex_g(a, b, c, d, &x, &y);
+    }
+    *re = x;
+    *im = y;
+}
+
+void qc_cmul(float a, float b, float c, float d, float out[2]) {
+    cmul(a, b, c, d, &out[0], &out[1]);
+}
+
 typedef struct {
     float eq[5][2];          /* eq_coeff   src/kalman.c:19 */
     float g[5][2];           /* kalman_gain src/kalman.c:20 */
@@ -168,19 +212,12 @@ static void kal_calc(kal_t *k, const float (*x)[2]) {
     for (int j = 1; j < 5; j++) {
         /* u0j*conj(x0) + conj(xj): the double-precision conj() sum rounds to
          * the fp32 sum (2p+2 <= 53), so it is an fp32 add. */
-        float ur = k->u[0][j][0], ui = k->u[0][j][1];
-        float cr = x[0][0], ci = -x[0][1];
-        float pr = ur * cr - ui * ci;
-        float pi = ur * ci + ui * cr;
+        float pr, pi;
+        cmul(k->u[0][j][0], k->u[0][j][1], x[0][0], -x[0][1], &pr, &pi);
         f[j][0] = pr + x[j][0];
         f[j][1] = pi + (-x[j][1]);
         for (int i = 1; i < j; i++) {
-            ur = k->u[i][j][0];
-            ui = k->u[i][j][1];
-            cr = x[i][0];
-            ci = -x[i][1];
-            pr = ur * cr - ui * ci;
-            pi = ur * ci + ui * cr;
+            cmul(k->u[i][j][0], k->u[i][j][1], x[i][0], -x[i][1], &pr, &pi);
             f[j][0] = f[j][0] + pr;
             f[j][1] = f[j][1] + pi;
         }
@@ -189,12 +226,16 @@ static void kal_calc(kal_t *k, const float (*x)[2]) {
         k->g[j][0] = f[j][0] * k->d[j];
         k->g[j][1] = f[j][1] * k->d[j];
     }
-    /* 6.5/6.6 a_j = a_{j-1} + Re(g_j * conj(f_j)) */
-    a[0] = E + (k->g[0][0] * f[0][0] - k->g[0][1] * (-f[0][1]));
-    for (int j = 1; j < 5; j++)
-        a[j] = a[j - 1] + (k->g[j][0] * f[j][0] - k->g[j][1] * (-f[j][1]));
+    /* 6.5/6.6 a_j = a_{j-1} + Re(g_j * conj(f_j)): crealf() of the full
+     * complex product, so the recovery sees its imaginary part too */
+    for (int j = 0; j < 5; j++) {
+        float tr, ti;
+        cmul(k->g[j][0], k->g[j][1], f[j][0], -f[j][1], &tr, &ti);
+        a[j] = (j == 0 ? E : a[j - 1]) + tr;
+    }
     const float hq = 1.0f + q;                 /* 6.7 */
     const float ht = a[4] * q;
+    if (!(a[4] + ht <= 0x1p125f) || a[4] + ht < 0.0f) t_div_range = 1;   /* diagnostics */
     float y = 1.0f / (a[0] + ht);              /* 6.19 */
     k->d[0] = k->d[0] * ((hq * (E + ht)) * y); /* 6.20 */
     for (int j = 1; j < 5; j++) {
@@ -205,13 +246,13 @@ static void kal_calc(kal_t *k, const float (*x)[2]) {
         k->d[j] = k->d[j] * ((hq * B) * y);    /* 6.13 */
         for (int i = 0; i < j; i++) {
             float b1r = k->u[i][j][0], b1i = k->u[i][j][1];
-            float gr = k->g[i][0], gi = -k->g[i][1];       /* conj(g_i) */
-            k->u[i][j][0] = b1r + (hr * gr - hi * gi);     /* 6.15 */
-            k->u[i][j][1] = b1i + (hr * gi + hi * gr);
-            float jr = k->g[j][0], ji = k->g[j][1];
-            float cr = b1r, ci = -b1i;                     /* conj(B1) */
-            k->g[i][0] = k->g[i][0] + (jr * cr - ji * ci); /* 6.16 */
-            k->g[i][1] = k->g[i][1] + (jr * ci + ji * cr);
+            float pr, pi;
+            cmul(hr, hi, k->g[i][0], -k->g[i][1], &pr, &pi);       /* h * conj(g_i) */
+            k->u[i][j][0] = b1r + pr;                              /* 6.15 */
+            k->u[i][j][1] = b1i + pi;
+            cmul(k->g[j][0], k->g[j][1], b1r, -b1i, &pr, &pi);     /* g_j * conj(B1) */
+            k->g[i][0] = k->g[i][0] + pr;                          /* 6.16 */
+            k->g[i][1] = k->g[i][1] + pi;
         }
     }
     k->y = y;
@@ -223,9 +264,10 @@ static void update_eq(kal_t *k, const float (*x)[2], float er, float ei) {
     er = er * k->y;
     ei = ei * k->y;
     for (int i = 0; i < 5; i++) {
-        float gr = k->g[i][0], gi = -k->g[i][1];
-        k->eq[i][0] = k->eq[i][0] + (er * gr - ei * gi);
-        k->eq[i][1] = k->eq[i][1] + (er * gi + ei * gr);
+        float pr, pi;
+        cmul(er, ei, k->g[i][0], -k->g[i][1], &pr, &pi);
+        k->eq[i][0] = k->eq[i][0] + pr;
+        k->eq[i][1] = k->eq[i][1] + pi;
     }
 }
 
@@ -233,9 +275,10 @@ static void update_eq(kal_t *k, const float (*x)[2], float er, float ei) {
 static float train_eq(kal_t *k, const float (*x)[2], float ref) {
     float vr = 0.0f, vi = 0.0f;
     for (int i = 0; i < 5; i++) {
-        float a = x[i][0], b = x[i][1], c = k->eq[i][0], d = k->eq[i][1];
-        vr = vr + (a * c - b * d);
-        vi = vi + (a * d + b * c);
+        float pr, pi;
+        cmul(x[i][0], x[i][1], k->eq[i][0], k->eq[i][1], &pr, &pi);
+        vr = vr + pr;
+        vi = vi + pi;
     }
     float er = ref - vr;   /* conjf(ref - val) = (ref - vr, vi) */
     float ei = vi;
@@ -248,9 +291,10 @@ static float train_eq(kal_t *k, const float (*x)[2], float ref) {
 static int data_eq(kal_t *k, const float (*x)[2], float soft[2]) {
     float sr = 0.0f, si = 0.0f;
     for (int i = 0; i < 5; i++) {
-        float a = x[i][0], b = x[i][1], c = k->eq[i][0], d = -k->eq[i][1];
-        sr = sr + (a * c - b * d);
-        si = si + (a * d + b * c);
+        float pr, pi;
+        cmul(x[i][0], x[i][1], k->eq[i][0], -k->eq[i][1], &pr, &pi);
+        sr = sr + pr;
+        si = si + pi;
     }
     int dI = sr < 0.0f;
     int dQ = si < 0.0f;
@@ -262,6 +306,24 @@ static int data_eq(kal_t *k, const float (*x)[2], float soft[2]) {
         soft[1] = si;
     }
     return (dI << 1) | dQ;
+}
+
+/* End of a segment: the GPU's one test per frame / data job is "a divisor left
+ * the reciprocal's range, or eq / u / d holds an inf or NaN now".  A segment
+ * with a both-NaN product that this test misses would keep the inline product
+ * where the reference's differs.  MUST mirror the kernels' test
+ * (singlecarrier_amd/csrc/qpsk_rx_back.h: kal_finite and the bmax check in
+ * train / data_steps); off unless a test sets qc_count_segments. */
+static void seg_end(const kal_t *k) {
+    if (!qc_count_segments) return;
+    int nonfin = 0;
+    for (int i = 0; i < 5; i++) {
+        nonfin |= !isfinite(k->eq[i][0]) || !isfinite(k->eq[i][1]) || !isfinite(k->d[i]);
+        for (int j = 0; j < 5; j++) nonfin |= !isfinite(k->u[i][j][0]) || !isfinite(k->u[i][j][1]);
+    }
+    if (nonfin || t_div_range) __atomic_fetch_add(&qc_flagged_segments, 1, __ATOMIC_RELAXED);
+    else if (t_both_nan) __atomic_fetch_add(&qc_unflagged_segments, 1, __ATOMIC_RELAXED);
+    t_both_nan = t_div_range = 0;
 }
 
 static int rx_frame(qc_chan_t *ch, const int16_t in[QC_FRAME], uint8_t bits[QC_BITS],
@@ -358,6 +420,7 @@ static int rx_frame(qc_chan_t *ch, const int16_t in[QC_FRAME], uint8_t bits[QC_B
     /* equalize(), src/qpsk.c:111-123 */
     kal_t k;
     kal_reset(&k);
+    t_both_nan = t_div_range = 0;
     int matches = 0;
     int dstep = QC_PRE;
     for (int i = 0; i < QC_PRE; i++) {
@@ -367,6 +430,7 @@ static int rx_frame(qc_chan_t *ch, const int16_t in[QC_FRAME], uint8_t bits[QC_B
         if (dstep == QC_PRE && (matches > QC_PRE - 30 || i + 1 - matches >= 30)) dstep = i + 1;
     }
     qc_decision_step = dstep;
+    seg_end(&k);
     const int valid = matches > QC_PRE - 30;  /* src/qpsk.c:196 */
     memset(bits, 0, QC_BITS);
     if (tr) memset(tr, 0, sizeof(*tr));
@@ -382,6 +446,7 @@ static int rx_frame(qc_chan_t *ch, const int16_t in[QC_FRAME], uint8_t bits[QC_B
                 tr->soft[s][1] = soft[1];
             }
         }
+        seg_end(&k);
         ch->rx_timing = mi + QC_PRE;  /* src/qpsk.c:219 */
     }
     if (tr) {

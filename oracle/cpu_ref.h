@@ -72,6 +72,29 @@ extern _Thread_local int qc_decision_step;
  * split FIR relies on: dec[255..289] only when mi >= 93).  Set it only while
  * no call runs. */
 extern int qc_poison_unobservable;
+/* Test switch (tests/test_oracle.py): when nonzero, the receive path's complex
+ * products stay (ac - bd, ad + bc) even where both parts are NaN, i.e. without
+ * the Annex G recovery the reference's gcc build performs.  It measures on
+ * which inputs that recovery is observable (tests/hostile.py's coverage
+ * condition).  Set it only while no call runs. */
+extern int qc_naive_cmul;
+/* Diagnostics (tests/test_oracle.py): the GPU kernels keep the inline product
+ * and test once per segment (a frame's training steps, a valid frame's data
+ * steps) whether a Kalman divisor left (0, 2^125] or eq / u / d ended with an
+ * inf or NaN; only then do they redo the segment with the whole product.
+ * qc_flagged_segments counts the segments that test catches,
+ * qc_unflagged_segments those where a product had both inline parts NaN and
+ * the test would NOT catch it: it must stay 0.  This is a model of kernel
+ * internals inside the oracle: it must mirror kal_finite and the bmax check
+ * of singlecarrier_amd/csrc/qpsk_rx_back.h, and proves nothing once they
+ * change without it.  Counted only while qc_count_segments is nonzero (off by
+ * default: the baseline and checker paths pay nothing); set and reset them
+ * only while no call runs. */
+extern long qc_unflagged_segments, qc_flagged_segments;
+extern int qc_count_segments;
+/* (a + bi)(c + di) -> out[0..1], the receive path's complex product: what gcc
+ * -O2 computes for a C99 `complex float` product (Annex G recovery included). */
+void qc_cmul(float a, float b, float c, float d, float out[2]);
 /* One qpsk_rx_frame() call.  bits[62] written (zero when invalid). */
 int qc_rx_frame(qc_chan_t *ch, const int16_t in[QC_FRAME], uint8_t bits[QC_BITS],
                 qc_trace_t *tr);

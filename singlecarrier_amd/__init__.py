@@ -57,7 +57,7 @@ def build(verbose: bool = False) -> str:
 
 # the receive kernels' sources and build rules, in the order the Makefile's KSRC
 # hashes them (csrc/Makefile: qpsk_kernel_hash())
-KERNEL_SOURCES = ("qpsk_rx.hip", "qpsk_rx_shared.h", "qpsk_herr.h", "qpsk_rx_dev.h", "qpsk_rx_front.h",
+KERNEL_SOURCES = ("qpsk_rx.hip", "qpsk_cmul.h", "qpsk_rx_shared.h", "qpsk_herr.h", "qpsk_rx_dev.h", "qpsk_rx_front.h",
                   "qpsk_rx_back.h", "qpsk_rx_quad.h", "qpsk_hunt.h", "qpsk_rcp.h", "qpsk_consts.h",
                   "qpsk_fft_dev.h", "qpsk_split.h", "Makefile")
 

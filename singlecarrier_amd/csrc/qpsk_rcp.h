@@ -8,13 +8,16 @@
 // returns the correctly rounded 1/x: tests/test_gpu_rcp.py checks it against
 // IEEE division for EVERY positive finite float (a bit-exact statement, not a
 // tolerance).  Outside that range (and for NaN) the exact division is used.
-// The operands here are a_j + ht >= E = 0.1, so the fallback never runs in
-// practice but keeps the function exact for all inputs.
+// The operands here are a_j + ht >= E = 0.1, so the low end is never met; the
+// high end, inf and NaN are: on tone-like full-scale input (sines, square and
+// triangle waves) the equalizer state overflows fp32 inside one frame, and the
+// frame or job is then recomputed on the exact path (qpsk_rx_back.h, `bad`).
+// On the modem's own signal that does not happen.
 #pragma once
 #include <hip/hip_runtime.h>
 
-// out of line: the (never taken in practice) exact path stays out of the hot
-// loop's register allocation
+// out of line: the exact path (rare: frames whose equalizer state leaves fp32
+// range) stays out of the hot loop's register allocation
 __device__ __attribute__((noinline)) float qk_div_ieee(float x) { return 1.0f / x; }
 
 // fast path only; callers check qk_rcp_in_range() on the operands themselves

@@ -11,45 +11,9 @@
 namespace {
 
 // ---------------------------------------------------------------- back role
-// Complex values are f2 = (re, im).  cmul(A, C) = (ac - bd, ad + bc) with every
-// product and the final sum/difference rounded once, exactly as gcc expands
-// the reference's complex products for finite operands: two packed multiplies
-// and one packed add (neg on the low half), no fusion.
-// (a.x - b.x, a.y + b.y) as ONE v_pk_add_f32 with the low half of b negated
-// (LLVM builds it from two packed adds plus moves otherwise); a + (-b) == a - b.
-__device__ __forceinline__ f2 addsub(f2 a, f2 b) {
-    f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// The two products, each ONE v_pk_mul_f32 with the broadcast/swap done by
-// op_sel (written out: LLVM otherwise copies the high half to a new register
-// before broadcasting it).
-__device__ __forceinline__ f2 mul_xx(f2 A, f2 C) {   // (A.x * C.x, A.x * C.y)
-    f2 r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(r) : "v"(A), "v"(C));
-    return r;
-}
-__device__ __forceinline__ f2 mul_yy_swap(f2 A, f2 C) {   // (A.y * C.y, A.y * C.x)
-    f2 r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0]" : "=v"(r) : "v"(A), "v"(C));
-    return r;
-}
-__device__ __forceinline__ f2 cmul(f2 A, f2 C) {
-    const f2 t1 = mul_xx(A, C);        // (ac, ad)
-    const f2 t2 = mul_yy_swap(A, C);   // (bd, bc)
-    return addsub(t1, t2);             // (ac - bd, ad + bc)
-}
-// A * conj(C) as the reference rounds it: (a*c - b*(-d), a*(-d) + b*c).  Since
-// b*(-d) == -(b*d) and a*(-d) == -(a*d) exactly, that is (ac + bd, -(ad) + bc):
-// the same two packed products and ONE packed add with the high half of t1 negated.
-__device__ __forceinline__ f2 cmulc(f2 A, f2 C) {
-    const f2 t1 = mul_xx(A, C);        // (ac, ad)
-    const f2 t2 = mul_yy_swap(A, C);   // (bd, bc)
-    f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_hi:[1,0]" : "=v"(r) : "v"(t1), "v"(t2));
-    return r;
-}
+// The complex products cmul / cmulc (inline form) and cmul_t / cmulc_t<EXACT>
+// (EXACT: with the Annex G recovery the reference's compiler adds) are in
+// qpsk_cmul.h.
 // a + conj(b) = (a.x + b.x, a.y + (-b.y)), one packed add
 __device__ __forceinline__ f2 addc(f2 a, f2 b) {
     f2 r;
@@ -69,10 +33,13 @@ __host__ __device__ constexpr int uix(int i, int j) { return j * (j - 1) / 2 + i
 
 // kalman_calculate (src/kalman.c:85-141) then update_eq (src/equalizer.c:25-40)
 // EXACT = false: the five divisions use the fast correctly-rounded reciprocal
-// (qpsk_rcp.h), valid inside [2^-125, 2^125]; `bad` collects lanes whose
-// operands left that range (never seen: they are >= 0.1), and the caller then
-// recomputes the whole frame with EXACT = true (IEEE division).  No branch in
-// the step, so the step is one basic block.
+// (qpsk_rcp.h), valid inside [2^-125, 2^125], and the complex products their
+// inline form (qpsk_cmul.h), which is the whole product while no value is
+// inf or NaN.  `bad` collects lanes whose frame left either premise -- tone-like
+// full-scale input does that: the equalizer state overflows fp32 inside a
+// frame -- and the caller then recomputes the whole frame with EXACT = true
+// (IEEE division, products with the Annex G recovery, 6.5/6.6 from the full
+// product).  No branch in the step, so the step is one basic block.
 // the gain half of update_eq: kalman_calculate (src/kalman.c:85-141); returns
 // kalman_y (the last 6.22 y).  It never reads eq or the error: the gain
 // recursion of a frame depends only on its window.
@@ -88,17 +55,20 @@ __device__ __forceinline__ float kal_gain(Kal& k, const f2 (&x)[5], unsigned& bm
 #pragma unroll
     for (int j = 1; j < 5; j++) {
         // u0j*conj(x0) + conj(xj) (the double conj() sum rounds to the fp32 sum)
-        f[j] = addc(cmulc(k.u[uix(0, j)], x[0]), x[j]);
+        f[j] = addc(cmulc_t<EXACT>(k.u[uix(0, j)], x[0]), x[j]);
 #pragma unroll
-        for (int i = 1; i < j; i++) f[j] = f[j] + cmulc(k.u[uix(i, j)], x[i]);
+        for (int i = 1; i < j; i++) f[j] = f[j] + cmulc_t<EXACT>(k.u[uix(i, j)], x[i]);
     }
 #pragma unroll
     for (int j = 0; j < 5; j++) k.g[j] = f[j] * k.d[j];   // 6.4  g = f*d (both halves d)
 #pragma unroll
     for (int j = 0; j < 5; j++) {                         // 6.5/6.6 Re(g * conj(f))
-        // gr*fr - gi*(-fi) == gr*fr + gi*fi (gi*(-fi) == -(gi*fi) exactly)
+        // gr*fr - gi*(-fi) == gr*fr + gi*fi (gi*(-fi) == -(gi*fi) exactly).
+        // EXACT: crealf() of the whole product, whose recovery looks at the
+        // imaginary part too
         const f2 t = k.g[j] * f[j];
-        a[j] = (j == 0 ? E : a[j - 1]) + (t.x + t.y);
+        const float re = EXACT ? cmulc_g(k.g[j], f[j]).x : t.x + t.y;
+        a[j] = (j == 0 ? E : a[j - 1]) + re;
     }
     const float hq = 1.0f + q;                            // 6.7
     const float ht = a[4] * q;
@@ -133,8 +103,8 @@ __device__ __forceinline__ float kal_gain(Kal& k, const f2 (&x)[5], unsigned& bm
 #pragma unroll
         for (int i = 0; i < j; i++) {
             const f2 B1 = k.u[uix(i, j)];
-            k.u[uix(i, j)] = B1 + cmulc(h, k.g[i]);          // 6.15
-            k.g[i] = k.g[i] + cmulc(k.g[j], B1);             // 6.16
+            k.u[uix(i, j)] = B1 + cmulc_t<EXACT>(h, k.g[i]);   // 6.15
+            k.g[i] = k.g[i] + cmulc_t<EXACT>(k.g[j], B1);      // 6.16
         }
     }
     return y;
@@ -147,7 +117,35 @@ __device__ __forceinline__ void update_eq(Kal& k, const f2 (&x)[5], f2 e, unsign
     const float y = kal_gain<EXACT>(k, x, bmax);
     e = e * y;                                            // error *= kalman_y
 #pragma unroll
-    for (int i = 0; i < 5; i++) k.eq[i] = k.eq[i] + cmulc(e, k.g[i]);
+    for (int i = 0; i < 5; i++) k.eq[i] = k.eq[i] + cmulc_t<EXACT>(e, k.g[i]);
+}
+
+// True unless eq, u or d holds an inf or a NaN (v * 0 is 0 for a finite v and
+// NaN otherwise; no contraction, no fast-math: the products stay).
+//
+// Why one test of the state after a frame's (or job's) steps finds every step
+// whose inline product was not the reference's.  The inline form differs from
+// the reference's product only where both of its parts are NaN, which takes an
+// inf or NaN among its operands or its four partial products.  Every product
+// of a step ends in the carried state or in the checked divisor:
+//   u*conj(x) -> f -> g = f*d -> Re(g conj f) -> a_j -> a_4 + ht   (bmax)
+//   h*conj(g) -> u;  g_j*conj(B1) -> g_i -> e*conj(g_i) -> eq;
+//   x*eq -> val -> e -> e*conj(g) -> eq
+// (an inf or NaN factor makes a product inf or NaN whatever the other factor
+// is, so `e * y` and `e * conj(g)` pass it on even through a zero).  And the
+// state keeps it: eq and u only ever change by `+=`, d by `*=`, and inf or NaN
+// plus or times anything is inf or NaN.  The state is reset per frame
+// (kal_reset), so nothing crosses into the next one.  The test is outside the
+// steps: finite frames run the loops they always ran.
+__device__ __forceinline__ bool kal_finite(const Kal& k) {
+    f2 z = {0.0f, 0.0f};
+#pragma unroll
+    for (int i = 0; i < 5; i++) z = z + k.eq[i] * 0.0f;
+#pragma unroll
+    for (int i = 0; i < 10; i++) z = z + k.u[i] * 0.0f;
+#pragma unroll
+    for (int i = 0; i < 5; i++) z = z + k.d[i] * 0.0f;
+    return z.x + z.y == 0.0f;
 }
 
 // A valid frame handed from the back wave to rx_data_kernel: the window
@@ -260,7 +258,7 @@ __device__ __forceinline__ int train(Kal& k, f2 (&x)[5], const f2* wp2, bool& ba
         const float ref = kPreTab.v[i];            // wave-uniform scalar load (kPreTab)
         f2 v = {0.0f, 0.0f};
 #pragma unroll
-        for (int t = 0; t < 5; t++) v = v + cmul(x[t], k.eq[t]);
+        for (int t = 0; t < 5; t++) v = v + cmul_t<EXACT>(x[t], k.eq[t]);
         const float er = ref - v.x;                // conjf(ref - val) = (ref - vr, vi)
         update_eq<EXACT>(k, x, f2{er, v.y}, bmax);
         if (er * ref > 0.0f) matches++;
@@ -268,7 +266,9 @@ __device__ __forceinline__ int train(Kal& k, f2 (&x)[5], const f2* wp2, bool& ba
         for (int t = 0; t < 4; t++) x[t] = x[t + 1];
         x[4] = nx;
     }
-    if (!EXACT) bad |= bmax > __float_as_uint(0x1p125f);
+    // out of the fast path's premises: a divisor outside the reciprocal's
+    // range, or an inf / NaN in the state (see kal_finite)
+    if (!EXACT) bad |= bmax > __float_as_uint(0x1p125f) || !kal_finite(k);
     return matches;
 }
 
@@ -350,7 +350,7 @@ __device__ __forceinline__ void data_step(Kal& k, f2 (&x)[5], f2 nx, int s, unsi
                                           float2* so, unsigned& bmax) {
     f2 sy = {0.0f, 0.0f};
 #pragma unroll
-    for (int t = 0; t < 5; t++) sy = sy + cmulc(x[t], k.eq[t]);
+    for (int t = 0; t < 5; t++) sy = sy + cmulc_t<EXACT>(x[t], k.eq[t]);
     const int dI = sy.x < 0.0f, dQ = sy.y < 0.0f;
     const f2 cst = {dI ? -1.0f : 1.0f, dQ ? -1.0f : 1.0f};
     update_eq<EXACT>(k, x, (cst - sy) * 0.1f, bmax);
@@ -382,7 +382,9 @@ __device__ __forceinline__ unsigned long long data_steps(Kal& k, f2 (&x)[5], con
 #pragma unroll
         for (int t = 0; t < R; t++) cur[t] = nxt[t];
     }
-    if (!EXACT) bad |= bmax > __float_as_uint(0x1p125f);
+    // as in train(): a job that starts from or reaches a non-finite state is
+    // redone with the reference's whole products
+    if (!EXACT) bad |= bmax > __float_as_uint(0x1p125f) || !kal_finite(k);
     return dib;
 }
 
@@ -418,7 +420,7 @@ __global__ void __launch_bounds__(256) rx_data_kernel(const float4* jobs, unsign
         float2* so = soft ? soft + j.cf * QK_NDSYM : nullptr;
         bool bad = force_exact != 0;
         unsigned long long dib = data_steps<false>(j.k, x, xs, so, bad);
-        if (__builtin_expect(bad, 0)) {   // recompute the job with IEEE division
+        if (__builtin_expect(bad, 0)) {   // recompute the job exactly (EXACT = true)
             get_job(jobs, cap, off, j);
 #pragma unroll
             for (int t = 0; t < 5; t++) x[t] = xs[t];

@@ -7,6 +7,7 @@
 
 #include <stdint.h>
 
+#include "qpsk_cmul.h"
 #include "qpsk_consts.h"
 #include "qpsk_hunt.h"
 #include "qpsk_rx_shared.h"
@@ -34,10 +35,7 @@ template <int MODE> struct Cfg;
 template <> struct Cfg<0> { static constexpr int kM = 1392, kDecBuf = 2; };
 template <> struct Cfg<1> { static constexpr int kM = 1750, kDecBuf = 1; };
 
-// (re, im) pairs as 2-wide vectors: a complex add / complex*real product is one
-// packed fp32 instruction (v_pk_add_f32 / v_pk_mul_f32: IEEE per lane, no
-// fusion), and the halves never need repacking.
-typedef float f2 __attribute__((ext_vector_type(2)));
+// (f2, the (re, im) pair type, comes from qpsk_cmul.h)
 
 constexpr unsigned long long kPreLo = qhunt::pre_mask(0), kPreHi = qhunt::pre_mask(1);
 

@@ -92,13 +92,16 @@ __device__ __forceinline__ f2 mul_dc(f2 f, f2 dd) {
 
 
 // one train_eq step (src/equalizer.c:45-58 with update_eq/kalman_calculate,
-// exactly update_eq<EXACT>'s operations) on the quad layout.  X0..X4 = x[c+1-d]
+// exactly update_eq<false>'s operations) on the quad layout.  X0..X4 = x[c+1-d]
 // (x[index+t] of the reference), zero before x[0].  Returns er = Re(error).
-// EXACT = false: `bmax` collects the bit patterns of the step's largest
-// reciprocal operand (xso, lane c: xs[c+1], nondecreasing in j, and >= xs[0]
-// >= E unless NaN); the caller tests bmax <= bits(2^125) once per frame, which
-// is qk_rcp_in_range() for every step (a NaN or -x has larger bits).
-template <bool EXACT>
+// Fast path only (fast reciprocal, inline complex products): `bmax` collects
+// the bit patterns of the step's largest reciprocal operand (xso, lane c:
+// xs[c+1], nondecreasing in j, and >= xs[0] >= E unless NaN); the caller tests
+// bmax <= bits(2^125) once per frame, which is qk_rcp_in_range() for every
+// step (a NaN or -x has larger bits).  There is no exact quad step: the zero
+// padding of this layout is multiplied by h and x, and 0 * inf is NaN, so a
+// frame whose state leaves fp32 range is redone a lane per channel
+// (back_frame_quad).
 __device__ __forceinline__ float qstep(QKal& k, const f2& X0, const f2& X1, const f2& X2, const f2& X3,
                                        const f2& X4, float ref, int c, unsigned& bmax) {
     const float E = QK_KAL_E, q = QK_KAL_Q;
@@ -143,13 +146,8 @@ __device__ __forceinline__ float qstep(QKal& k, const f2& X0, const f2& X1, cons
     const float ap = c == 0 ? a0 : c == 1 ? a1 : c == 2 ? a2 : a3;   // a[c]
     const float ao = ap + s;                              // a[c+1], the chain's own add
     const f2 xs = f2{a0, ao} + f2{ht, ht};               // (xs[0], xs[c+1]), 6.19 / 6.22 operands
-    f2 y;
-    if (EXACT) {
-        y = f2{qk_div_ieee(xs.x), qk_div_ieee(xs.y)};
-    } else {
-        bmax = max(bmax, __float_as_uint(xs.y));
-        y = f2{qk_rcp_fast(xs.x), qk_rcp_fast(xs.y)};
-    }
+    bmax = max(bmax, __float_as_uint(xs.y));
+    const f2 y = f2{qk_rcp_fast(xs.x), qk_rcp_fast(xs.y)};
     // 6.20 / 6.21+6.13: d[0] *= (hq * (E + ht)) * y0, d[c+1] *= (hq * (a[c] + ht)) * y[c+1]
     k.dd = k.dd * ((f2{hq, hq} * (f2{E, ap} + f2{ht, ht})) * y);
     const float y0 = y.x, yo = y.y;
@@ -211,7 +209,7 @@ __device__ __forceinline__ void qload_x0(const f2* wp2, int c, f2 (&X)[5]) {
 // roles repeat every iteration and no register moves at the back edge; the
 // sample of step s+4 is loaded right after step s, into the slot step s read
 // last (reads run to step 131, inside the 168-slot window row).
-template <bool EXACT, typename PollFn>
+template <typename PollFn>
 __device__ __forceinline__ int qtrain(QKal& k, const f2 (&X)[5], const f2* wl, int c, bool& bad, PollFn poll) {
     int matches = 0;
     unsigned bmax = 0u;
@@ -231,13 +229,62 @@ __device__ __forceinline__ int qtrain(QKal& k, const f2 (&X)[5], const f2* wl, i
         for (int t = 0; t < 8; t++) {
             if ((t & 3) == 0) poll();   // every 4 steps (dynamic priority, rx_kernel kDyn)
             const float ref = ref8[t];
-            const float er = qstep<EXACT>(k, w[t & 7], w[(t + 7) & 7], w[(t + 6) & 7], w[(t + 5) & 7],
+            const float er = qstep(k, w[t & 7], w[(t + 7) & 7], w[(t + 6) & 7], w[(t + 5) & 7],
                                           w[(t + 4) & 7], ref, c, bmax);
             matches += (er * ref > 0.0f) ? 1 : 0;
             w[(t + 4) & 7] = wl[i + t + 4];   // sample of step i+t+4
         }
     }
-    if (!EXACT) bad |= bmax > __float_as_uint(0x1p125f);
+    // the fast path's premises, as in train(): the divisors inside the
+    // reciprocal's range and the state finite (kal_finite's argument holds for
+    // the quad layout's real entries, which undergo the same operations; a
+    // padding entry can only add an inf or NaN, never hide one).  Lanes 0..2
+    // accumulate an unused eq4: it is left out.
+    f2 z = k.eqr * 0.0f + k.dd * 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) z = z + k.R[i] * 0.0f;
+    if (c == 3) z = z + k.eq4 * 0.0f;
+    bad |= bmax > __float_as_uint(0x1p125f) || !(z.x + z.y == 0.0f);
+    return matches;
+}
+
+// The lanes of `vm` (at most one per quad) each append a job: one slot
+// reservation per wave, then lane `mine` stores its job.
+__device__ __forceinline__ void quad_push_jobs(float4* jobs, size_t jcap, unsigned* njobs,
+                                               unsigned long long vm, bool mine, const DataJob& j,
+                                               const f2* x35) {
+    unsigned base = 0;
+    if (lane_id() == 0) base = atomicAdd(njobs, (unsigned)__popcll(vm));
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (mine) {
+        const unsigned slot = base + (unsigned)__popcll(vm & ((1ull << lane_id()) - 1ull));
+        put_job(jobs, jcap, slot, j, x35);
+    }
+}
+
+// The exact recomputation of a quad wave's frames (a `bad` lane in the wave):
+// every lane of a quad runs its channel's lane-per-channel training on the
+// same window slots, and valid frames' jobs take that state.  Returns matches.
+// Called by the whole wave.  Out of line, job store included, so that the lane
+// state (Kal, 50 VGPRs) never meets the quad loop's register allocation; the
+// training's priority polls are left out (rare path).
+__device__ __attribute__((noinline)) int quad_redo_frame(const float2* win, bool live, bool lead,
+                                                         float4* jobs, size_t jcap,
+                                                         unsigned* njobs, size_t cf, unsigned ks) {
+    const f2* wp2 = reinterpret_cast<const f2*>(win);
+    DataJob j;
+    j.k = kal_reset();
+    f2 x[5];
+    load_x0(reinterpret_cast<const float4*>(win), x);
+    bool bad = true;
+    const int matches = train<true>(j.k, x, wp2, bad, [] {});
+    const bool mine = live && lead && matches > QK_MATCH_MIN;
+    const unsigned long long vm = __ballot(mine);
+    if (vm) {
+        j.cf = cf;
+        j.ks = ks;
+        quad_push_jobs(jobs, jcap, njobs, vm, mine, j, wp2 + 129);
+    }
     return matches;
 }
 
@@ -254,15 +301,18 @@ __device__ __forceinline__ void back_frame_quad(const RxArgs& a, int ch, bool li
     f2 X[5];
     qload_x0(wp2, c, X);
     bool bad = roles_force_exact(a.roles);
-    int matches = qtrain<false>(k, X, wp2 + c + 2, c, bad, poll);
-    if (__builtin_expect(__ballot(bad) != 0ull, 0)) {   // recompute the frame exactly
-        k = qkal_reset();
-        qload_x0(wp2, c, X);
-        matches = qtrain<true>(k, X, wp2 + c + 2, c, bad, poll);
+    int matches = qtrain(k, X, wp2 + c + 2, c, bad, poll);
+    const size_t cf = (size_t)ch * a.F + n;
+    const unsigned ks = (a.g0 + (unsigned)n) % QK_KS_FRAMES;
+    // a lane left the fast path's premises: the wave's frames are recomputed
+    // exactly, and their jobs stored, out of line (wave-uniform branch)
+    const bool redo = __ballot(bad) != 0ull;
+    if (__builtin_expect(redo, 0)) {
+        poll();   // the priority this frame's training would run at
+        matches = quad_redo_frame(win, live, lead, a.jobs, a.jcap, a.njobs, cf, ks);
     }
     const bool valid = live && matches > QK_MATCH_MIN;   // src/qpsk.c:196
-    const size_t cf = (size_t)ch * a.F + n;
-    const unsigned long long vm = __ballot(valid && lead);
+    const unsigned long long vm = redo ? 0ull : __ballot(valid && lead);
     if (vm) {   // gather the quad's state (all lanes take part in the DPP moves)
         DataJob j;
         j.k.eq[0] = qd2<qd::kB0>(k.eqr);
@@ -283,15 +333,9 @@ __device__ __forceinline__ void back_frame_quad(const RxArgs& a, int ch, bool li
         j.k.d[2] = f2{d2, d2};
         j.k.d[3] = f2{d3, d3};
         j.k.d[4] = f2{d4, d4};
-        unsigned base = 0;
-        if (lane_id() == 0) base = atomicAdd(a.njobs, (unsigned)__popcll(vm));
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (valid && lead) {
-            const unsigned slot = base + (unsigned)__popcll(vm & ((1ull << lane_id()) - 1ull));
-            j.cf = cf;
-            j.ks = (a.g0 + (unsigned)n) % QK_KS_FRAMES;
-            put_job(a.jobs, a.jcap, slot, j, wp2 + 129);
-        }
+        j.cf = cf;
+        j.ks = ks;
+        quad_push_jobs(a.jobs, a.jcap, a.njobs, vm, valid && lead, j, wp2 + 129);
     }
     if (live && !valid) {   // invalid frame: bits (and soft symbols) are zero
         uint16_t* bo = reinterpret_cast<uint16_t*>(a.bits + cf * QK_NBITS);

@@ -9,6 +9,8 @@ below comes from oracle/_ref/libqpsk_ref.so, i.e. the reference's own code.
 
     python tests/golden/make_golden.py            # everything
     python tests/golden/make_golden.py --dec752   # only the dec752-mode fixtures
+    python tests/golden/make_golden.py --hostile  # only hostile_ref.npz
+    python tests/golden/make_golden.py --hostile-sweep   # re-choose hostile_params.json, then --hostile
 
 The dec752 fixtures ("intended semantics"; NOT reference
 parity) come from oracle/_ref/libqpsk_ref752.so: the same unmodified reference
@@ -93,8 +95,160 @@ def dec752():
     print("sample (dec752):", exp["output_md5"], exp["output_bytes"], "B")
 
 
+# ------------------------------------------------------------ hostile corpus
+# tests/hostile.py's parameter table and its reference-made golden.
+HOSTILE_AMPS = [32767, 30000, 20000, 10000, 3000]
+HOSTILE_GOLDEN = (32, 8)   # channels x frames of hostile_ref.npz (the table's first rows)
+
+
+def _hostile_candidates(n, seed):
+    """n candidate wave rows: every second one a single triangle (the family
+    with the most channels on which the Annex G recovery is observable), the
+    others cycling through squares, two-wave sums and gated triangles."""
+    rng = np.random.default_rng(seed)
+
+    def one(kind):
+        return {"kind": kind, "k": int(rng.integers(800, 32001)),
+                "p": int(rng.integers(0, 65536)), "a": int(rng.choice(HOSTILE_AMPS))}
+
+    rows = []
+    for i in range(n):
+        kind = ["tri", "square", "tri2", "sq2", "sqtri", "gated"][i % 6] if i % 2 else "tri"
+        if kind in ("tri", "square"):
+            r = one(kind)
+        elif kind == "gated":
+            r = dict(one("tri"), gate=int(rng.integers(4, 40)))
+        else:
+            r = {"sum": [one({"tri2": "tri", "sq2": "square", "sqtri": "square"}[kind]),
+                         one("square" if kind == "sq2" else "tri")]}
+        rows.append(r)
+    return rows
+
+
+def _differs(a, b):
+    """[nch][nframes] mask: any documented output differs (soft: valid frames, bitwise)."""
+    (b1, v1, t1), (b2, v2, t2) = a, b
+    m = (v1 != v2) | (b1 != b2).any(-1)
+    for k in ("max_index", "matches", "rx_timing"):
+        m |= t1[k] != t2[k]
+    soft = (t1["soft"].view(np.uint32) != t2["soft"].view(np.uint32)).any((-1, -2))
+    return m | (v1.astype(bool) & v2.astype(bool) & soft)
+
+
+def _hostile_impaired():
+    rows = []
+    for i, (d, num) in enumerate((d, num) for d in (3, 7, 25, 60) for num in (2, -2, 1)):
+        rows.append({"kind": "echo", "seed": 301, "c": i, "d": d, "num": num})
+    for i, g in enumerate((4, 100, 4, 100, 4, 100)):
+        rows.append({"kind": "gain", "seed": 302, "c": i, "g": g})
+    for i, o in enumerate((5000, -5000, 12000, -12000, 20000, -20000)):
+        rows.append({"kind": "dc", "seed": 303, "c": i, "o": o})
+    for i, at in enumerate((2000, 3000, 5000, 7000, 9400, 11000, 13000, 15000)):
+        rows.append({"kind": "step", "seed": 304, "c": i, "at": at, "sh": 10})
+    return rows
+
+
+def hostile_sweep(ncand=6144, seed=20):
+    """Choose the rows of tests/golden/hostile_params.json.  Every measurement
+    below is on the unmodified reference (oracle/_ref) and on the restatement
+    with qc_naive_cmul set, never on the code under test:
+      sensitive channel-frame: the naive-product restatement departs from the
+        reference there (reference mode, or dec752 for the second set);
+      non-finite valid frame: the reference calls it valid and its soft
+        symbols hold an inf or a NaN."""
+    import ctypes
+    sys.path.insert(0, os.path.dirname(HERE))
+    import hostile
+    assert oracle.ref_available() and oracle.ref_available(oracle.MODE_DEC752)
+    flag = ctypes.c_int.in_dll(oracle.cpu_lib(), "qc_naive_cmul")
+    rows = _hostile_candidates(ncand, seed)
+    x = hostile.waves(rows)
+    sens = {}
+    for mode in (oracle.MODE_REF, oracle.MODE_DEC752):
+        ref = oracle.ref_rx(x, trace=True, mode=mode)
+        flag.value = 1
+        try:
+            naive = oracle.cpu_rx(x, trace=True, mode=mode)
+        finally:
+            flag.value = 0
+        sens[mode] = _differs(naive, ref)
+        if mode == oracle.MODE_REF:
+            nonfin = ref[1].astype(bool) & ~np.isfinite(ref[2]["soft"]).all((-1, -2))
+    s0, s1 = sens[oracle.MODE_REF], sens[oracle.MODE_DEC752]
+    gch, gfr = HOSTILE_GOLDEN
+    chosen = []
+
+    def take(mask, n, exact=True):
+        """Append up to n not yet chosen candidates of mask; the rows whose
+        position the tests rely on must all be found (exact)."""
+        got = 0
+        for c in np.where(mask)[0]:
+            if got == n:
+                break
+            if c not in chosen:
+                chosen.append(int(c))
+                got += 1
+        assert got == n or not exact, (got, n)
+        return got
+
+    take(s0[:, :4].any(1), 8)             # rows 0..7: the tiny host call (4 frames)
+    take(s0[:, :gfr].any(1), 12)          # the golden's sensitive channels ...
+    nsens = len(chosen)                   # rows 0..nsens-1: sensitive inside the golden's frames
+    assert s0[chosen, :gfr].any(1).all() and s0[chosen[:8], :4].any(1).all()
+    take(nonfin[:, :gfr].any(1), 8)       # ... its non-finite valid ones ...
+    take(s1[:, :gfr].any(1), 4)           # ... and dec752-only ones: 32 rows
+    assert len(chosen) == gch
+    take(s0.any(1), 36)
+    take(nonfin.any(1), 16, exact=False)  # all there are
+    take(s1.any(1), 28)
+    take(np.ones(len(rows), bool), 160 - len(chosen))   # the rest: the families as they come
+    assert len(chosen) == 160
+    out = {"nframes": hostile.NFRAMES,
+           "golden": {"channels": gch, "frames": gfr, "sensitive": nsens},
+           "wave": [rows[c] for c in chosen], "impaired": _hostile_impaired()}
+    with open(hostile.PARAMS, "w") as f:
+        f.write("{\n")
+        for k in ("nframes", "golden"):
+            f.write(' "%s": %s,\n' % (k, json.dumps(out[k])))
+        for k in ("wave", "impaired"):
+            f.write(' "%s": [\n  ' % k + ",\n  ".join(json.dumps(r) for r in out[k])
+                    + ("\n ],\n" if k == "wave" else "\n ]\n"))
+        f.write("}\n")
+    print("hostile sweep: %d candidates, sensitive cf %d / ch %d (ref), %d / %d (dec752), "
+          "non-finite valid frames %d in %d ch" % (ncand, s0.sum(), s0.any(1).sum(), s1.sum(),
+                                                   s1.any(1).sum(), nonfin.sum(), nonfin.any(1).sum()))
+    print("chosen: sensitive cf %d / ch %d, non-finite valid %d / ch %d" % (
+        s0[chosen].sum(), s0[chosen].any(1).sum(), nonfin[chosen].sum(), nonfin[chosen].any(1).sum()))
+
+
+def hostile_golden():
+    """tests/golden/hostile_ref.npz: the reference's outputs (both builds) on
+    the first rows and frames of the corpus, soft symbols of valid frames only."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import hostile
+    gch, gfr = HOSTILE_GOLDEN
+    x = np.ascontiguousarray(hostile.waves(hostile.params()["wave"][:gch], gfr))
+    out = {"input_sha256": hashlib.sha256(x.tobytes()).hexdigest()}
+    for tag, mode in (("ref", oracle.MODE_REF), ("d752", oracle.MODE_DEC752)):
+        b, v, t = oracle.ref_rx(x, trace=True, mode=mode)
+        vm = v.astype(bool)
+        out.update({tag + "_bits": np.packbits(b, axis=-1), tag + "_valid": v,
+                    tag + "_max_index": t["max_index"].astype(np.int16),
+                    tag + "_matches": t["matches"].astype(np.int16),
+                    tag + "_rx_timing": t["rx_timing"].astype(np.int16),
+                    tag + "_soft": t["soft"][vm].view(np.uint32)})   # bit patterns: NaNs kept
+        print("hostile golden", tag, "valid", int(vm.sum()), "non-finite valid",
+              int((~np.isfinite(t["soft"][vm]).all((-1, -2))).sum()))
+    np.savez_compressed(os.path.join(HERE, "hostile_ref.npz"), **out)
+
+
 def main():
     oracle.build(ref=True)
+    if "--hostile-sweep" in sys.argv[1:]:
+        hostile_sweep()
+        return hostile_golden()
+    if "--hostile" in sys.argv[1:]:
+        return hostile_golden()
     if "--dec752" in sys.argv[1:]:
         return dec752()
     assert oracle.ref_available()
@@ -154,6 +308,7 @@ def main():
                         lengths=np.array([len(s) for s, _ in syms]), samples=np.concatenate(out))
     print("sample:", exp["output_md5"], exp["output_bytes"], "B")
     dec752()
+    hostile_golden()
 
 
 if __name__ == "__main__":

@@ -340,7 +340,8 @@ def test_quad_back_edges_and_noise(ebn0, width, monkeypatch):
 @pytest.mark.parametrize("width", [None, "32"])
 def test_quad_back_exact_division(width, monkeypatch):
     """QPSK_FORCE_EXACT on the quad back (100 channels: W = 16, or W = 32
-    forced: two back waves per frame chain): the IEEE-division retrain path."""
+    forced: two back waves per frame chain): the exact retrain path, which a
+    quad wave runs a lane per channel (back_frame_quad)."""
     monkeypatch.setenv("QPSK_FORCE_EXACT", "1")
     if width:
         monkeypatch.setenv("QPSK_WIDTH", width)

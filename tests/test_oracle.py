@@ -166,6 +166,9 @@ def test_edge_inputs_vs_reference():
     np.testing.assert_array_equal(b1, b2)
     for k in ("max_index", "matches", "rx_timing"):
         np.testing.assert_array_equal(t1[k], t2[k])
+    vm = v2.astype(bool)
+    assert vm.any()
+    np.testing.assert_array_equal(t1["soft"][vm].view(np.uint32), t2["soft"][vm].view(np.uint32))
 
 
 @pytest.mark.parametrize("ebn0", [1000.0, 6.0, 2.0])
@@ -360,3 +363,146 @@ def test_decimated_frame_dec752_vs_padded_reference():
     ref_dec = oracle.ref_stages(x, mode=oracle.MODE_DEC752)[0]
     dec = oracle.cpu_stages(x, mode=oracle.MODE_DEC752)
     np.testing.assert_array_equal(dec.view(np.uint32), ref_dec.view(np.uint32))
+
+
+# ------------------------------------------------------------ hostile inputs
+# tests/hostile.py: int16 streams (square / triangle waves, their sums, gated
+# triangles; integer impairments of the modem's own signal) on which the
+# reference's equalizer state leaves fp32 range inside a frame.  There the
+# reference's C99 complex products take gcc's Annex G recovery (both parts NaN
+# -> infinities), which the restatement's cmul() follows; qc_naive_cmul turns
+# that off to measure where it is observable.
+import hostile  # noqa: E402
+
+HOSTILE_MODES = [oracle.MODE_REF, oracle.MODE_DEC752]
+
+
+def _hostile_outputs(r):
+    bits, valid, tr = r
+    vm = valid.astype(bool)
+    return {"valid": valid, "bits": bits, "max_index": tr["max_index"], "matches": tr["matches"],
+            "rx_timing": tr["rx_timing"], "soft": tr["soft"][vm].view(np.uint32)}
+
+
+def _naive(x, mode):
+    import ctypes
+    flag = ctypes.c_int.in_dll(oracle.cpu_lib(), "qc_naive_cmul")
+    flag.value = 1
+    try:
+        return oracle.cpu_rx(x, trace=True, mode=mode)
+    finally:
+        flag.value = 0
+
+
+def _departs(a, b):
+    """[nch][nframes]: some documented output differs (soft: frames both call valid)."""
+    (b1, v1, t1), (b2, v2, t2) = a, b
+    m = (v1 != v2) | (b1 != b2).any(-1)
+    for k in ("max_index", "matches", "rx_timing"):
+        m |= t1[k] != t2[k]
+    soft = (t1["soft"].view(np.uint32) != t2["soft"].view(np.uint32)).any((-1, -2))
+    return m | (v1.astype(bool) & v2.astype(bool) & soft)
+
+
+def test_hostile_corpus_shape():
+    p = hostile.params()
+    assert len(p["wave"]) + len(p["impaired"]) == 192 and p["nframes"] == hostile.NFRAMES == 12
+    for name in ("wave", "impaired"):
+        x = hostile.group(name)
+        assert x.dtype == np.int16 and x.shape == (len(p[name]), 12, oracle.FRAME)
+    assert np.abs(hostile.group("wave").astype(np.int32)).max() == 32767
+
+
+@pytest.mark.skipif(not oracle.ref_available(), reason="reference build not present")
+def test_hostile_coverage_on_the_reference():
+    """The corpus' reason to exist, measured on the unmodified reference (never
+    on the code under test), in reference mode: at least 32 channel-frames in
+    at least 24 channels where the naive-product restatement departs from the
+    reference, and at least 8 valid frames in at least 4 channels whose
+    reference soft symbols are not finite."""
+    x = hostile.group("wave")
+    ref = oracle.ref_rx(x, trace=True)
+    sens = _departs(_naive(x, oracle.MODE_REF), ref)
+    assert sens.sum() >= 32 and sens.any(1).sum() >= 24, (sens.sum(), sens.any(1).sum())
+    nonfin = ref[1].astype(bool) & ~np.isfinite(ref[2]["soft"]).all((-1, -2))
+    assert nonfin.sum() >= 8 and nonfin.any(1).sum() >= 4, (nonfin.sum(), nonfin.any(1).sum())
+    # the tiny-call rows (tests/test_gpu_hostile.py): sensitive inside 4 frames
+    assert sens[:8, :4].any(1).all()
+    # the golden's sensitive rows: sensitive inside the golden's frames
+    gd = hostile.params()["golden"]
+    assert sens[:gd["sensitive"], :gd["frames"]].any(1).all()
+    # the impaired group is the finite side: large soft symbols, near-threshold
+    # match counts, nothing non-finite
+    b, v, t = oracle.ref_rx(hostile.group("impaired"), trace=True)
+    soft = t["soft"][v.astype(bool)]
+    assert np.isfinite(soft).all() and np.abs(soft).max() > 1e6
+    assert ((t["matches"] >= 94) & (t["matches"] <= 103)).sum() >= 8
+
+
+@pytest.mark.parametrize("mode", HOSTILE_MODES)
+def test_hostile_corpus_vs_reference(mode):
+    """Restatement == reference on the whole corpus: valid, bits, max_index,
+    matches, rx_timing, and the soft symbols of valid frames bit for bit (NaN
+    payloads included), in reference mode and in dec752 against the padded
+    build."""
+    if not oracle.ref_available(mode):
+        pytest.skip("oracle/_ref not built (no /root/reference here)")
+    for name in ("wave", "impaired"):
+        got = _hostile_outputs(hostile.expected(name, mode))
+        exp = _hostile_outputs(oracle.ref_rx(hostile.group(name), trace=True, mode=mode))
+        for k in exp:
+            np.testing.assert_array_equal(got[k], exp[k], err_msg=f"{name} {k}")
+
+
+@pytest.mark.parametrize("tag,mode", [("ref", oracle.MODE_REF), ("d752", oracle.MODE_DEC752)])
+def test_hostile_golden(golden_dir, tag, mode):
+    """The same against the reference-made golden (hostile_ref.npz: the
+    table's first 32 rows x 8 frames, both reference builds), which needs no
+    reference build; and the naive product departs from it."""
+    g = np.load(os.path.join(golden_dir, "hostile_ref.npz"))
+    gd = hostile.params()["golden"]
+    nch, nf = gd["channels"], gd["frames"]
+    x = np.ascontiguousarray(hostile.waves(hostile.params()["wave"][:nch], nf))
+    assert hashlib.sha256(x.tobytes()).hexdigest() == str(g["input_sha256"])
+    np.testing.assert_array_equal(x, hostile.group("wave")[:nch, :nf])   # a prefix of the corpus
+
+    def check(r):
+        got = _hostile_outputs(r)
+        np.testing.assert_array_equal(got["valid"], g[tag + "_valid"])
+        np.testing.assert_array_equal(np.packbits(got["bits"], axis=-1), g[tag + "_bits"])
+        for k in ("max_index", "matches", "rx_timing"):
+            np.testing.assert_array_equal(got[k], g[tag + "_" + k])
+        np.testing.assert_array_equal(got["soft"], g[tag + "_soft"])
+
+    check(oracle.cpu_rx(x, trace=True, mode=mode))
+    with pytest.raises(AssertionError):
+        check(_naive(x, mode))
+    soft = g[tag + "_soft"].view(np.float32)
+    assert mode != oracle.MODE_REF or (~np.isfinite(soft)).any()
+
+
+@pytest.mark.parametrize("naive", [1, 0])
+def test_hostile_inline_product_departures_are_all_detectable(naive):
+    """The premise of the kernels' fast path (qpsk_rx_back.h kal_finite): a
+    segment -- a frame's 128 training steps, a valid frame's 31 data steps --
+    in which some product has both inline parts NaN always ends with an inf
+    or NaN in eq / u / d, or had a Kalman divisor outside (0, 2^125].  Counted
+    by the restatement itself on the whole corpus, along the inline-product
+    trajectory the kernels follow (qc_naive_cmul) and along the reference's."""
+    import ctypes
+    lib = oracle.cpu_lib()
+    flag = ctypes.c_int.in_dll(lib, "qc_naive_cmul")
+    missed = ctypes.c_long.in_dll(lib, "qc_unflagged_segments")
+    caught = ctypes.c_long.in_dll(lib, "qc_flagged_segments")
+    counting = ctypes.c_int.in_dll(lib, "qc_count_segments")
+    missed.value = caught.value = 0
+    flag.value = naive
+    counting.value = 1
+    try:
+        for mode in HOSTILE_MODES:
+            for name in ("wave", "impaired"):
+                oracle.cpu_rx(hostile.group(name), trace=True, mode=mode)
+    finally:
+        flag.value = counting.value = 0
+    assert missed.value == 0
+    assert caught.value >= 100   # most wave frames overflow; the impaired group never does
