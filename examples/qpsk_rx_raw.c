@@ -4,12 +4,17 @@
  *
  *   qpsk_rx_raw in.raw out.bin            single channel, qpsk_rx_frame() per frame
  *                                          (unchanged reference call pattern)
- *   qpsk_rx_raw -b [-m MODE] in1.raw [in2.raw ...] -o PREFIX
+ *   qpsk_rx_raw -b [-m MODE] [-f FMT] in1.raw [in2.raw ...] -o PREFIX
  *                                          every file is one channel; all channels are
  *                                          demodulated together through qpsk_rx_batch()
  *                                          and PREFIX<i>.bin is written per channel;
  *                                          MODE = QPSK_MODE_* (qpsk_batch.h, default 0:
- *                                          the reference; 1 dec752, 2 FFT hunt, 3 both)
+ *                                          the reference; 1 dec752, 2 FFT hunt, 3 both);
+ *                                          FMT = s16 (default), alaw or ulaw: the files
+ *                                          hold 8-bit G.711 codes, 1880 to a frame, which
+ *                                          cross PCIe as they are and are expanded on the
+ *                                          GPU (qpsk_rx_batch_fmt, qpsk_input.h)
+ *   qpsk_rx_raw -f FMT in.g711 out.bin     one channel of G.711 codes, the same way
  * Output: one 496-byte record per valid frame, bits in bytes 0..61 (the
  * reference's /tmp/databits.txt format, src/qpsk.c:455-457).
  * Build: gcc -O2 -Iinclude qpsk_rx_raw.c -Lsinglecarrier_amd -lqpsk_hip -Wl,-rpath,...
@@ -19,17 +24,19 @@
 #include <string.h>
 
 #include "qpsk_batch.h"
+#include "qpsk_input.h"
 #include "qpsk_internal.h"
 
-static int16_t *read_frames(const char *path, int *nframes) {
+/* the whole frames of a file whose samples are `es` bytes each */
+static void *read_frames(const char *path, size_t es, int *nframes) {
     FILE *f = fopen(path, "rb");
     if (!f) return NULL;
     fseek(f, 0, SEEK_END);
     long bytes = ftell(f);
     fseek(f, 0, SEEK_SET);
-    *nframes = (int)(bytes / (long)(sizeof(int16_t) * FRAME_SIZE));  /* short tail dropped */
-    int16_t *buf = malloc(sizeof(int16_t) * (size_t)(*nframes > 0 ? *nframes : 1) * FRAME_SIZE);
-    if (buf && fread(buf, sizeof(int16_t) * FRAME_SIZE, (size_t)*nframes, f) != (size_t)*nframes) {
+    *nframes = (int)(bytes / (long)(es * FRAME_SIZE));  /* short tail dropped */
+    void *buf = malloc(es * (size_t)(*nframes > 0 ? *nframes : 1) * FRAME_SIZE);
+    if (buf && fread(buf, es * FRAME_SIZE, (size_t)*nframes, f) != (size_t)*nframes) {
         free(buf);
         buf = NULL;
     }
@@ -61,19 +68,21 @@ static int single(const char *in, const char *out) {
     return 0;
 }
 
-static int batch(int nch, char **paths, const char *prefix, int mode) {
+/* prefix: PREFIX<i>.bin per channel; else one channel to the file `single_out` */
+static int batch(int nch, char **paths, const char *prefix, const char *single_out, int mode, int fmt) {
     int nf = -1;
-    int16_t **ch = calloc((size_t)nch, sizeof(int16_t *));
+    const size_t es = fmt == QPSK_IN_S16 ? sizeof(int16_t) : 1;
+    void **ch = calloc((size_t)nch, sizeof(void *));
     for (int c = 0; c < nch; c++) {
         int n;
-        ch[c] = read_frames(paths[c], &n);
+        ch[c] = read_frames(paths[c], es, &n);
         if (!ch[c]) return 1;
         if (nf < 0 || n < nf) nf = n;   /* common length: frames every channel has */
     }
     if (nf <= 0) return 1;
-    int16_t *in = malloc(sizeof(int16_t) * (size_t)nch * nf * FRAME_SIZE);
+    char *in = malloc(es * (size_t)nch * nf * FRAME_SIZE);
     for (int c = 0; c < nch; c++)
-        memcpy(in + (size_t)c * nf * FRAME_SIZE, ch[c], sizeof(int16_t) * (size_t)nf * FRAME_SIZE);
+        memcpy(in + es * (size_t)c * nf * FRAME_SIZE, ch[c], es * (size_t)nf * FRAME_SIZE);
     uint8_t *bits = malloc((size_t)nch * nf * 62), *valid = malloc((size_t)nch * nf);
     int err;
     qpsk_ctx *ctx = qpsk_rx_create_mode(0, nch, mode, &err);
@@ -81,7 +90,7 @@ static int batch(int nch, char **paths, const char *prefix, int mode) {
         fprintf(stderr, "qpsk: %s\n", qpsk_strerror(err));
         return 3;
     }
-    err = qpsk_rx_batch(ctx, in, nf, bits, valid, NULL, NULL);
+    err = qpsk_rx_batch_fmt(ctx, in, fmt | QPSK_IN_PLANAR, 0, nf, bits, valid, NULL, NULL);
     if (err) {
         fprintf(stderr, "qpsk: %s\n", qpsk_strerror(err));
         return 3;
@@ -89,7 +98,8 @@ static int batch(int nch, char **paths, const char *prefix, int mode) {
     uint8_t rec[BITS_PER_FRAME];
     for (int c = 0; c < nch; c++) {
         char name[4096];
-        snprintf(name, sizeof name, "%s%d.bin", prefix, c);
+        if (prefix) snprintf(name, sizeof name, "%s%d.bin", prefix, c);
+        else snprintf(name, sizeof name, "%s", single_out);
         FILE *fo = fopen(name, "wb");
         if (!fo) return 1;
         for (int n = 0; n < nf; n++) {
@@ -104,17 +114,28 @@ static int batch(int nch, char **paths, const char *prefix, int mode) {
     return 0;
 }
 
+static int format_of(const char *name) {
+    return !strcmp(name, "s16") ? QPSK_IN_S16 : !strcmp(name, "alaw") ? QPSK_IN_ALAW
+         : !strcmp(name, "ulaw") ? QPSK_IN_ULAW : -1;
+}
+
 int main(int argc, char **argv) {
-    if (argc >= 3 && strcmp(argv[1], "-b") != 0) return single(argv[1], argv[2]);
+    if (argc == 5 && !strcmp(argv[1], "-f") && format_of(argv[2]) >= 0)
+        return batch(1, argv + 3, NULL, argv[4], QPSK_MODE_REFERENCE, format_of(argv[2]));
+    if (argc >= 3 && strcmp(argv[1], "-b") != 0 && strcmp(argv[1], "-f") != 0) return single(argv[1], argv[2]);
     if (argc >= 5 && !strcmp(argv[1], "-b") && !strcmp(argv[argc - 2], "-o")) {
-        int first = 2, mode = QPSK_MODE_REFERENCE;
-        if (argc >= 7 && !strcmp(argv[2], "-m")) {
-            mode = atoi(argv[3]);
-            first = 4;
+        int first = 2, mode = QPSK_MODE_REFERENCE, fmt = QPSK_IN_S16;
+        if (argc >= first + 5 && !strcmp(argv[first], "-m")) {
+            mode = atoi(argv[first + 1]);
+            first += 2;
         }
-        return batch(argc - 2 - first, argv + first, argv[argc - 1], mode);
+        if (argc >= first + 5 && !strcmp(argv[first], "-f")) {
+            fmt = format_of(argv[first + 1]);
+            first += 2;
+        }
+        if (fmt >= 0) return batch(argc - 2 - first, argv + first, argv[argc - 1], NULL, mode, fmt);
     }
-    fprintf(stderr, "usage: %s in.raw out.bin | -b [-m MODE] in1.raw [in2.raw ...] -o PREFIX\n",
-            argv[0]);
+    fprintf(stderr, "usage: %s in.raw out.bin | -f FMT in.g711 out.bin | -b [-m MODE] [-f FMT] in1.raw "
+                    "[in2.raw ...] -o PREFIX   (FMT: s16, alaw, ulaw)\n", argv[0]);
     return 2;
 }

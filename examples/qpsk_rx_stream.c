@@ -7,8 +7,15 @@
  * 496-byte records go to PREFIX<i>.bin, as the reference writes them
  * (src/qpsk.c:455-457).
  *
- *   qpsk_rx_stream [-f FRAMES_PER_CHUNK] in1.raw [in2.raw ...] -o PREFIX
+ *   qpsk_rx_stream [-f FRAMES_PER_CHUNK] [-f FMT] in1.raw [in2.raw ...] -o PREFIX
+ *   qpsk_rx_stream [-f FRAMES_PER_CHUNK] [-f FMT] -i NCH trunk.raw -o PREFIX
  *
+ * FMT = s16 (default), alaw or ulaw: the files hold 8-bit G.711 codes, which go
+ * into the pinned slots and over PCIe as they are and are expanded on the GPU
+ * (qpsk_stream_create_fmt, include/qpsk_input.h).  -i NCH: the one input file
+ * is a timeslot-interleaved trunk, one sample of each of the NCH channels after
+ * another; a chunk of it is a slot's block as it stands, de-interleaved on the
+ * GPU.
  * Channels end at the shortest file (whole frames only, as the reference).
  * Build: make -C examples
  */
@@ -17,6 +24,7 @@
 #include <string.h>
 
 #include "qpsk_batch.h"
+#include "qpsk_input.h"
 #include "qpsk_internal.h"
 #include "qpsk_stream.h"
 
@@ -34,29 +42,42 @@ static void drain(qpsk_stream *s, int nch, int frames, int nf_chunk, FILE **out,
     }
 }
 
+static void usage(const char *argv0) {
+    fprintf(stderr, "usage: %s [-f FRAMES_PER_CHUNK] [-f s16|alaw|ulaw] (in1.raw [in2.raw ...] | -i NCH trunk.raw) "
+                    "-o PREFIX\n", argv0);
+}
+
 int main(int argc, char **argv) {
-    int frames = 8, a = 1;
-    if (argc > 2 && !strcmp(argv[1], "-f")) {
-        frames = atoi(argv[2]);
-        a = 3;
+    int frames = 8, a = 1, fmt = QPSK_IN_S16, trunk = 0;
+    while (a + 1 < argc && (!strcmp(argv[a], "-f") || !strcmp(argv[a], "-i"))) {
+        const char *v = argv[a + 1];
+        if (!strcmp(argv[a], "-i")) trunk = atoi(v);
+        else if (!strcmp(v, "s16")) fmt = QPSK_IN_S16;
+        else if (!strcmp(v, "alaw")) fmt = QPSK_IN_ALAW;
+        else if (!strcmp(v, "ulaw")) fmt = QPSK_IN_ULAW;
+        else frames = atoi(v);
+        a += 2;
     }
-    if (argc - a < 3 || strcmp(argv[argc - 2], "-o") || frames < 1) {
-        fprintf(stderr, "usage: %s [-f FRAMES_PER_CHUNK] in1.raw [in2.raw ...] -o PREFIX\n", argv[0]);
+    if (argc - a < 3 || strcmp(argv[argc - 2], "-o") || frames < 1 || trunk < 0 || (trunk && argc - a != 3)) {
+        usage(argv[0]);
         return 2;
     }
-    const int nch = argc - a - 2;
+    const int nfile = argc - a - 2, nch = trunk ? trunk : nfile;
+    const size_t es = fmt == QPSK_IN_S16 ? sizeof(int16_t) : 1;
+    if (trunk) fmt |= QPSK_IN_INTERLEAVED;
     const char *prefix = argv[argc - 1];
-    FILE **in = calloc((size_t)nch, sizeof(FILE *)), **out = calloc((size_t)nch, sizeof(FILE *));
+    FILE **in = calloc((size_t)nfile, sizeof(FILE *)), **out = calloc((size_t)nch, sizeof(FILE *));
     for (int c = 0; c < nch; c++) {
         char name[4096];
         snprintf(name, sizeof name, "%s%d.bin", prefix, c);
-        in[c] = fopen(argv[a + c], "rb");
+        if (c < nfile && !(in[c] = fopen(argv[a + c], "rb"))) return 1;
         out[c] = fopen(name, "wb");
-        if (!in[c] || !out[c]) return 1;
+        if (!out[c]) return 1;
     }
     const int nslot = 3;
     int err;
-    qpsk_stream *s = qpsk_stream_create(0, nch, frames, nslot, &err);
+    /* (planar int16 is the plain stream: qpsk_stream_create) */
+    qpsk_stream *s = qpsk_stream_create_fmt(0, nch, frames, nslot, QPSK_MODE_REFERENCE, fmt, &err);
     if (!s) {
         fprintf(stderr, "qpsk: %s\n", qpsk_strerror(err));
         return 3;
@@ -69,17 +90,21 @@ int main(int argc, char **argv) {
             drain(s, nch, frames, sizes[retrieved % nslot], out, rec);
             retrieved++;
         }
-        int16_t *buf = qpsk_stream_acquire(s, &err);
+        char *buf = qpsk_stream_acquire_raw(s, &err);
         if (!buf) {
             fprintf(stderr, "qpsk: %s\n", qpsk_strerror(err));
             return 3;
         }
         /* every channel contributes the same number of whole frames */
         int nf = frames;
-        for (int c = 0; c < nch; c++) {
-            size_t got = fread(buf + (size_t)c * frames * FRAME_SIZE, sizeof(int16_t) * FRAME_SIZE,
-                               (size_t)nf, in[c]);                           /* src/qpsk.c:442 */
-            if ((int)got < nf) nf = (int)got;
+        if (trunk) {   /* FRAME_SIZE rows of nch samples make a frame of every channel */
+            nf = (int)fread(buf, es * FRAME_SIZE * (size_t)nch, (size_t)frames, in[0]);
+        } else {
+            for (int c = 0; c < nch; c++) {
+                size_t got = fread(buf + es * (size_t)c * frames * FRAME_SIZE, es * FRAME_SIZE,
+                                   (size_t)nf, in[c]);                       /* src/qpsk.c:442 */
+                if ((int)got < nf) nf = (int)got;
+            }
         }
         if (nf < frames) done = 1;   /* the shortest stream ended inside this chunk */
         if (nf == 0) break;
@@ -97,7 +122,7 @@ int main(int argc, char **argv) {
     }
     qpsk_stream_destroy(s);
     for (int c = 0; c < nch; c++) {
-        fclose(in[c]);
+        if (c < nfile) fclose(in[c]);
         fclose(out[c]);
     }
     free(rec);

@@ -1,0 +1,88 @@
+/*
+ * qpsk_input.h -- input formats of the receive path: 8-bit G.711 codes (A-law,
+ * mu-law) and timeslot-interleaved blocks, converted on the GPU to the layout
+ * qpsk_rx_batch() takes.  Many 8 kHz channels reach a host as G.711 codes, one
+ * sample of every channel after another; converting on the device halves the
+ * bytes that cross PCIe and removes the host's expand-and-transpose pass.
+ *
+ * A format word is  encoding | layout.
+ *   encoding  QPSK_IN_S16   int16 linear samples (little endian)
+ *             QPSK_IN_ALAW  8-bit G.711 A-law codes
+ *             QPSK_IN_ULAW  8-bit G.711 mu-law codes
+ *   layout    QPSK_IN_PLANAR       [nch][T]: channel c's samples are contiguous
+ *             QPSK_IN_INTERLEAVED  element (t, c) is src[t * ld + c]; ld >= nch
+ *                                  counts elements, so a channel range of a
+ *                                  wider trunk is a pointer and its ld
+ * with T = nframes * 1880.  For planar input ld is ignored.  The output is
+ * always int16 [nch][nframes][1880].
+ *
+ * G.711 decoding is the exact integer expansion of ITU-T G.711 to 16 bits:
+ *   mu-law  u = ~code;  t = (((u & 15) << 3) + 0x84) << ((u >> 4) & 7);
+ *           value = (u & 0x80) ? 0x84 - t : t - 0x84
+ *   A-law   a = code ^ 0x55;  m = (a & 15) << 4;  s = (a >> 4) & 7;
+ *           v = s == 0 ? m + 8 : s == 1 ? m + 0x108 : (m + 0x108) << (s - 1);
+ *           value = (a & 0x80) ? v : -v
+ * (mu-law 0x00 -> -32124, 0x80 -> 32124, 0x7F and 0xFF -> 0; A-law 0x55 -> -8,
+ * 0xD5 -> 8, 0x2A -> -32256, 0xAA -> 32256).
+ *
+ * Errors are those of qpsk_batch.h.  Every argument check runs before any HIP
+ * call.  QPSK_EINVAL: an unknown format word, ld < nch with interleaved
+ * layout, a NULL pointer with nframes > 0, nch < 1, nframes < 0,
+ * nch * nframes >= 2^28.
+ */
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "qpsk_batch.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+enum {
+    QPSK_IN_S16 = 0,
+    QPSK_IN_ALAW = 1,
+    QPSK_IN_ULAW = 2,
+    QPSK_IN_PLANAR = 0,
+    QPSK_IN_INTERLEAVED = 0x10,
+};
+
+/* Bytes of a source block from its first element to its last: nch * T elements
+ * planar, (T - 1) * ld + nch interleaved; 0 for nframes == 0 and for arguments
+ * the conversions refuse. */
+size_t qpsk_input_bytes(int fmt, int nch, int nframes, long ld);
+
+/* The conversion on the host (plain C, `nthreads` threads over channels): the
+ * contract of qpsk_input_convert_device, and what a caller without a GPU at
+ * hand expands with. */
+int qpsk_input_convert_host(int fmt, const void *src, long ld, int nch, int nframes,
+                            int16_t *out, int nthreads);
+
+/* The conversion on the device, enqueued on `stream` (a hipStream_t, NULL =
+ * default stream) without synchronising.  Writes exactly nch * T int16 to
+ * d_out and nothing else.  d_out is 16-byte aligned; d_src may have any
+ * alignment its element size allows (odd addresses for 8-bit codes) and must
+ * not overlap d_out.  Both are device pointers of the current device. */
+int qpsk_input_convert_device(int fmt, const void *d_src, long ld, int nch, int nframes,
+                              int16_t *d_out, void *stream);
+
+/* qpsk_rx_batch() for input in format `fmt`: copies the source block as it is
+ * over PCIe, converts it on the device and receives.  Returns what
+ * qpsk_rx_batch() returns. */
+int qpsk_rx_batch_fmt(qpsk_ctx *ctx, const void *in, int fmt, long ld, int nframes,
+                      uint8_t *bits, uint8_t *valid, int32_t *trace, float *soft);
+
+/* qpsk_rx_batch_device() for device input in format `fmt`: the conversion and
+ * the receive are enqueued on `stream`.  The converted block lives in a device
+ * buffer the context owns, which only grows (a call larger than every earlier
+ * one waits for the device before it reallocates).  For QPSK_IN_S16 |
+ * QPSK_IN_PLANAR both calls are the plain ones: no copy, no buffer. */
+int qpsk_rx_batch_device_fmt(qpsk_ctx *ctx, const void *d_in, int fmt, long ld, int nframes,
+                             uint8_t *d_bits, uint8_t *d_valid, int32_t *d_trace,
+                             float *d_soft, void *stream);
+
+#ifdef __cplusplus
+}
+#endif

@@ -39,9 +39,20 @@ qpsk_stream *qpsk_stream_create(int device, int nch, int frames, int nslot, int 
 /* the same with the receiver semantics `mode` (QPSK_MODE_*, qpsk_batch.h) */
 qpsk_stream *qpsk_stream_create_mode(int device, int nch, int frames, int nslot, int mode,
                                      int *err);
+/* the same for chunks in input format `fmt` (QPSK_IN_*, qpsk_input.h): a slot's
+ * pinned input is then the source block of qpsk_input_bytes(fmt, nch, frames,
+ * nch) bytes (interleaved chunks have ld = nch), qpsk_stream_submit copies
+ * those bytes and converts them on the receive stream in front of the receive.
+ * With QPSK_IN_S16 | QPSK_IN_PLANAR it is qpsk_stream_create_mode. */
+qpsk_stream *qpsk_stream_create_fmt(int device, int nch, int frames, int nslot, int mode,
+                                    int fmt, int *err);
 void qpsk_stream_destroy(qpsk_stream *s);
-/* pinned input buffer of the next chunk, or NULL (*err = QPSK_EBUSY) */
+/* pinned input buffer of the next chunk, or NULL (*err = QPSK_EBUSY; QPSK_EINVAL
+ * on a stream whose format is not planar int16: its input is not int16
+ * [nch][frames][1880], use qpsk_stream_acquire_raw) */
 int16_t *qpsk_stream_acquire(qpsk_stream *s, int *err);
+/* the same for a stream of any format: the slot's pinned source block */
+void *qpsk_stream_acquire_raw(qpsk_stream *s, int *err);
 /* enqueue the acquired chunk; returns 0 or a negative QPSK_E* code */
 int qpsk_stream_submit(qpsk_stream *s);
 /* chunks submitted and not yet retrieved */

@@ -2,8 +2,9 @@
 
 Python mirror of the C-ABI in ``include/qpsk_internal.h`` (the reference's
 ``headers/qpsk_internal.h:79-84`` surface) and ``include/qpsk_batch.h`` (the
-batched, multi-channel receiver) and ``include/qpsk_tx.h`` (the batched
-transmitter), over ``singlecarrier_amd/libqpsk_hip.so``.
+batched, multi-channel receiver), ``include/qpsk_tx.h`` (the batched
+transmitter) and ``include/qpsk_input.h`` (G.711 and timeslot-interleaved
+input), over ``singlecarrier_amd/libqpsk_hip.so``.
 
 There is no CPU fallback: if the HIP library is missing or no GPU is present,
 the receive functions raise.  (The CPU restatement in ``oracle/`` is test
@@ -164,6 +165,18 @@ def lib():
         L.qpsk_tx_batch_host.argtypes = [vp, i32, vp, i32, i32, vp, C.c_long, i32]
         L.qpsk_tx_state_init.restype = None
         L.qpsk_tx_state_init.argtypes = [vp]
+        L.qpsk_input_bytes.restype = C.c_size_t
+        L.qpsk_input_bytes.argtypes = [i32, i32, i32, C.c_long]
+        L.qpsk_input_convert_host.argtypes = [i32, vp, C.c_long, i32, i32, vp, i32]
+        L.qpsk_input_convert_device.argtypes = [i32, vp, C.c_long, i32, i32, vp, vp]
+        L.qpsk_input_convert_device_dec.argtypes = [i32, vp, C.c_long, i32, i32, vp, vp, i32]
+        L.qpsk_input_load_width.argtypes = [vp, C.c_long, i32]
+        L.qpsk_rx_batch_fmt.argtypes = [vp, vp, i32, C.c_long, i32, vp, vp, vp, vp]
+        L.qpsk_rx_batch_device_fmt.argtypes = [vp, vp, i32, C.c_long, i32, vp, vp, vp, vp, vp]
+        L.qpsk_stream_create_fmt.restype = vp
+        L.qpsk_stream_create_fmt.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int)]
+        L.qpsk_stream_acquire_raw.restype = vp
+        L.qpsk_stream_acquire_raw.argtypes = [vp, C.POINTER(C.c_int)]
         L.cnormf.restype = C.c_float
         L.cnormf.argtypes = [_CF]   # _Complex float == {float, float} in one SSE reg (SysV)
         _lib = L
@@ -184,7 +197,10 @@ SYMBOLS = ["qpsk_rx_create", "qpsk_rx_create_mode", "qpsk_rx_mode", "qpsk_rx_des
            "qpsk_rx_state_save", "qpsk_rx_state_load",
            "qpsk_tx_create", "qpsk_tx_destroy", "qpsk_tx_reset", "qpsk_tx_channels", "qpsk_tx_gap",
            "qpsk_tx_packets", "qpsk_tx_batch", "qpsk_tx_batch_device", "qpsk_tx_sync",
-           "qpsk_tx_batch_host"]
+           "qpsk_tx_batch_host",
+           "qpsk_input_bytes", "qpsk_input_convert_host", "qpsk_input_convert_device",
+           "qpsk_rx_batch_fmt", "qpsk_rx_batch_device_fmt", "qpsk_stream_create_fmt",
+           "qpsk_stream_acquire_raw"]
 
 
 def _check(rc: int) -> None:
@@ -206,6 +222,117 @@ def _ptr(a) -> int | None:
 MODE_REFERENCE = 0   # bit-identical to the reference as built
 MODE_DEC752 = 1      # decimated_frame[752] ("intended semantics"), NOT reference parity
 MODE_FFT_HUNT = 2    # flag: preamble hunt through the reference's kiss_fft (src/fft.c)
+
+
+# input formats (include/qpsk_input.h): a format word is encoding | layout
+IN_S16, IN_ALAW, IN_ULAW = 0, 1, 2
+IN_PLANAR, IN_INTERLEAVED = 0, 0x10
+
+
+def _in_dtype(fmt: int):
+    return np.int16 if (fmt & 0x0f) == IN_S16 else np.uint8
+
+
+def _fmt_check(fmt: int, nch: int) -> None:
+    """QPSK_EINVAL for an unknown format word or nch < 1 (the library's own
+    check: a call of no frames)."""
+    _check(lib().qpsk_input_convert_host(fmt, None, nch, nch, 0, None, 1))
+
+
+def _in_block(x, fmt: int, nch: int, what: str = "x"):
+    """(nframes, ld) of a source block in format `fmt`: planar [nch][T],
+    interleaved [T][ld] with ld >= nch (a 2-D array or tensor whose rows are
+    ld elements apart and whose elements along a row are adjacent; the columns
+    past nch need not belong to it), T = nframes * 1880.  Works on numpy
+    arrays and torch tensors alike."""
+    shape = tuple(x.shape)
+    inter = (fmt & ~0x0f) == IN_INTERLEAVED
+    if inter:
+        if len(shape) != 2 or shape[1] != nch or shape[0] % FRAME_SIZE:
+            raise ValueError(f"{what} must be [nframes * {FRAME_SIZE}][{nch}], got {shape}")
+        return shape[0] // FRAME_SIZE, None
+    n = 1
+    for d in shape[1:]:
+        n *= d
+    if len(shape) < 2 or shape[0] != nch or n % FRAME_SIZE:
+        raise ValueError(f"{what} must be [{nch}][nframes * {FRAME_SIZE}], got {shape}")
+    return n // FRAME_SIZE, 0
+
+
+def _np_block(x, fmt: int, nch: int):
+    """A numpy source block as (array that owns the memory, nframes, ld).  An
+    interleaved block may be a column range of a wider array (ld = its row
+    length) and may start at any element; anything else is made contiguous."""
+    x = np.asarray(x)
+    if x.dtype != _in_dtype(fmt):
+        raise ValueError(f"format {fmt:#x} takes {np.dtype(_in_dtype(fmt)).name} input, got {x.dtype}")
+    nf, ld = _in_block(x, fmt, nch)
+    if ld is None:
+        es = x.itemsize
+        if x.shape[0] > 1 and (x.strides[1] != es or x.strides[0] % es or x.strides[0] < nch * es):
+            x = np.ascontiguousarray(x)
+        elif x.shape[0] <= 1 and x.strides[1] != es:
+            x = np.ascontiguousarray(x)
+        ld = x.strides[0] // es if x.shape[0] > 1 else nch
+    elif not x.flags.c_contiguous:
+        x = np.ascontiguousarray(x)
+    return x, nf, ld
+
+
+def input_bytes(fmt: int, nch: int, nframes: int, ld: int = 0) -> int:
+    """qpsk_input_bytes: bytes of a source block from its first element to its
+    last (0 for arguments the conversions refuse)."""
+    return int(lib().qpsk_input_bytes(fmt, nch, nframes, ld))
+
+
+def input_convert_host(x, fmt: int, nch: int, threads: int = 0) -> np.ndarray:
+    """qpsk_input_convert_host: a source block in format `fmt` (planar
+    [nch][T] or interleaved [T][nch], possibly a column range of a wider
+    array) -> int16 [nch][nframes][1880], on the host."""
+    _fmt_check(fmt, nch)
+    x, nf, ld = _np_block(x, fmt, nch)
+    out = np.empty((nch, nf, FRAME_SIZE), np.int16)
+    threads = threads or min(16, os.cpu_count() or 1)
+    _check(lib().qpsk_input_convert_host(fmt, _ptr(x), ld, nch, nf, _ptr(out), threads))
+    return out
+
+
+def _torch_block(x, fmt: int, nch: int):
+    """(nframes, ld) of a cuda tensor in format `fmt`; an interleaved block may
+    be a column range of a wider tensor."""
+    import torch
+    want = torch.int16 if (fmt & 0x0f) == IN_S16 else torch.uint8
+    if not x.is_cuda or x.dtype != want:
+        raise ValueError(f"format {fmt:#x} takes a cuda {want} tensor")
+    nf, ld = _in_block(x, fmt, nch)
+    if ld is None:
+        if (x.shape[0] > 1 and (x.stride(1) != 1 or x.stride(0) < nch)) or \
+                (x.shape[0] <= 1 and nch > 1 and x.stride(1) != 1):
+            raise ValueError("an interleaved block must have unit stride along a row and rows >= nch apart")
+        ld = x.stride(0) if x.shape[0] > 1 else nch
+    elif not x.is_contiguous():
+        raise ValueError("a planar block must be contiguous")
+    return nf, ld
+
+
+def input_convert_device(x, fmt: int, nch: int, out=None, stream=None):
+    """qpsk_input_convert_device: a cuda tensor in format `fmt` -> a torch int16
+    tensor [nch][nframes][1880] on the same device; enqueued on ``stream``
+    (default: torch's current stream)."""
+    import torch
+    _fmt_check(fmt, nch)
+    nf, ld = _torch_block(x, fmt, nch)
+    if out is None:
+        out = torch.empty((nch, nf, FRAME_SIZE), dtype=torch.int16, device=x.device)
+    elif out.dtype != torch.int16 or tuple(out.shape) != (nch, nf, FRAME_SIZE) or not out.is_contiguous() \
+            or not out.is_cuda:
+        raise ValueError(f"out must be a contiguous cuda int16 [{nch}][{nf}][{FRAME_SIZE}] tensor")
+    with torch.cuda.device(x.device):
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        _check(lib().qpsk_input_convert_device(fmt, x.data_ptr(), ld, nch, nf, out.data_ptr(),
+                                               C.c_void_p(stream.cuda_stream)))
+    return out
 
 
 class Receiver:
@@ -289,6 +416,42 @@ class Receiver:
         _check(lib().qpsk_rx_batch(self._h, _ptr(x), nf, _ptr(out["bits"]), _ptr(out["valid"]),
                                    _ptr(out.get("trace")), _ptr(out.get("soft"))))
         return out
+
+    def demod_fmt(self, x, fmt: int, trace: bool = False, soft: bool = False):
+        """``demod`` for a host source block in format ``fmt`` (IN_*): planar
+        [nch][nframes * 1880] or interleaved [nframes * 1880][nch] (possibly a
+        column range of a wider array: ld is its row length), int16 or uint8
+        G.711 codes.  The block crosses PCIe as it is and is converted on the
+        GPU (qpsk_rx_batch_fmt)."""
+        _fmt_check(fmt, self.nch)
+        x, nf, ld = _np_block(x, fmt, self.nch)
+        out = {"bits": np.zeros((self.nch, nf, NBITS), np.uint8),
+               "valid": np.zeros((self.nch, nf), np.uint8)}
+        if trace:
+            out["trace"] = np.zeros((self.nch, nf, 4), np.int32)
+        if soft:
+            out["soft"] = np.zeros((self.nch, nf, DATA_SYMBOLS, 2), np.float32)
+        _check(lib().qpsk_rx_batch_fmt(self._h, _ptr(x), fmt, ld, nf, _ptr(out["bits"]),
+                                       _ptr(out["valid"]), _ptr(out.get("trace")), _ptr(out.get("soft"))))
+        return out
+
+    def demod_device_fmt(self, x, fmt: int, bits, valid, trace=None, soft=None, stream=None) -> None:
+        """``demod_device`` for a cuda source block in format ``fmt`` (layouts
+        as demod_fmt): conversion and receive are enqueued on ``stream``
+        (qpsk_rx_batch_device_fmt)."""
+        import torch
+        _fmt_check(fmt, self.nch)
+        nf, ld = _torch_block(x, fmt, self.nch)
+        for name, t, shape in (("bits", bits, (self.nch, nf, NBITS)),
+                               ("valid", valid, (self.nch, nf)),
+                               ("trace", trace, (self.nch, nf, 4)),
+                               ("soft", soft, (self.nch, nf, DATA_SYMBOLS, 2))):
+            if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError(f"{name} must be a contiguous cuda tensor of shape {shape}")
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        _check(lib().qpsk_rx_batch_device_fmt(self._h, x.data_ptr(), fmt, ld, nf, _ptr(bits), _ptr(valid),
+                                              _ptr(trace), _ptr(soft), C.c_void_p(stream.cuda_stream)))
 
     def sync(self) -> None:
         """Wait for the latest demod_device call; raise QpskError (QPSK_ESTALL)
@@ -426,15 +589,20 @@ def tx_batch_host(bits, gap: int = 903, states=None, threads: int = 0) -> np.nda
 class Stream:
     """Streaming ingest over pinned chunk slots (include/qpsk_stream.h): fill
     ``acquire()`` in place, ``submit()``, later ``retrieve()`` the oldest chunk.
-    Every channel's state carries across chunks."""
+    Every channel's state carries across chunks.  With ``fmt`` other than
+    planar int16 (IN_*) the chunks are source blocks in that format, filled
+    through ``acquire_raw()`` and converted on the GPU."""
 
     def __init__(self, nch: int, frames: int, nslot: int = 3, device: int = 0,
-                 mode: int = MODE_REFERENCE):
+                 mode: int = MODE_REFERENCE, fmt: int = IN_S16 | IN_PLANAR):
         err = C.c_int(0)
-        self._h = lib().qpsk_stream_create_mode(device, nch, frames, nslot, mode, C.byref(err))
+        if fmt == IN_S16 | IN_PLANAR:
+            self._h = lib().qpsk_stream_create_mode(device, nch, frames, nslot, mode, C.byref(err))
+        else:
+            self._h = lib().qpsk_stream_create_fmt(device, nch, frames, nslot, mode, fmt, C.byref(err))
         if not self._h:
             _check(err.value or -3)
-        self.nch, self.frames, self.nslot = nch, frames, nslot
+        self.nch, self.frames, self.nslot, self.fmt = nch, frames, nslot, fmt
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -452,6 +620,21 @@ class Stream:
         n = self.nch * self.frames * FRAME_SIZE
         buf = (C.c_int16 * n).from_address(p)
         return np.frombuffer(buf, np.int16).reshape(self.nch, self.frames, FRAME_SIZE)
+
+    def acquire_raw(self) -> np.ndarray:
+        """The next chunk's pinned source block in the stream's format: planar
+        [nch][frames * 1880], interleaved [frames * 1880][nch]; int16 or uint8."""
+        err = C.c_int(0)
+        p = lib().qpsk_stream_acquire_raw(self._h, C.byref(err))
+        if not p:
+            _check(err.value or -1)
+        dt = _in_dtype(self.fmt)
+        n = self.nch * self.frames * FRAME_SIZE
+        buf = (C.c_uint8 * (n * np.dtype(dt).itemsize)).from_address(p)
+        a = np.frombuffer(buf, dt)
+        if (self.fmt & ~0x0f) == IN_INTERLEAVED:
+            return a.reshape(self.frames * FRAME_SIZE, self.nch)
+        return a.reshape(self.nch, self.frames * FRAME_SIZE)
 
     def submit(self) -> None:
         _check(lib().qpsk_stream_submit(self._h))

@@ -1,0 +1,363 @@
+// qpsk_input.hip -- qpsk_input_convert_device (include/qpsk_input.h): G.711
+// codes and timeslot-interleaved blocks to the receive path's int16
+// [nch][nframes][1880], on the GPU.  Two kernels, both bound by memory:
+//
+//   planar_kernel       [nch][T] codes -> [nch][T] int16, a flat pass: a lane
+//                       takes 16 codes and stores 2 x 16 bytes.  Groups follow
+//                       the output, which is 16-byte aligned, so every store is;
+//                       a source at any byte address is read as the two aligned
+//                       16-byte words around a group, shifted by the call's one
+//                       byte offset.  The groups whose aligned words would reach
+//                       outside the block (the first, the last ones) and the
+//                       tail go per element.
+//   interleaved_kernel  src[t * ld + c] -> [nch][T]: a tile of 64 channels x 128
+//                       samples through LDS.  Global loads run along the channel
+//                       axis, W bytes a lane (W chosen per call from the
+//                       alignment of the source and of ld); the tile is kept as
+//                       it was read, rows of 64 elements padded by one dword.
+//                       Then a lane gathers 8 samples of one channel down the
+//                       rows, decodes, and stores 16 bytes along time: a wave
+//                       stores 128-byte runs of 8 channels.  LDS banking of both
+//                       sides: DESIGN.md (f2).
+//
+// G.711 is decoded either with the integer expansion (qpsk_input_fmt.h) or
+// through a 256-entry table in LDS that each block makes with it;
+// qpsk_input_convert_device_dec names one, profiles/input_bench.py times both,
+// and the default is the faster of each kernel (qpsk_input_internal.h).
+// The format entry points of the receive path and of the streams are here
+// too, on the hooks of qpsk_rx_internal.h: the receive and stream units refer
+// to nothing of this file.
+// Not part of the receive kernels' hash (csrc/Makefile KSRC).
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "qpsk_consts.h"
+#include "qpsk_herr.h"
+#include "qpsk_input.h"
+#include "qpsk_input_fmt.h"
+#include "qpsk_input_internal.h"
+#include "qpsk_rx_internal.h"
+#include "qpsk_stream.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kTC = 64;          // channels of a tile
+constexpr int kTT = 128;         // samples of a tile
+constexpr unsigned kMaxGrid = 1u << 20;
+
+template <int ENC, int DEC>
+__device__ __forceinline__ unsigned decode(unsigned code, const int16_t* tab) {
+    if constexpr (ENC == QPSK_IN_S16) return code;
+    else if constexpr (DEC == QPSK_IN_DEC_TABLE) return (unsigned)(uint16_t)tab[code];
+    else if constexpr (ENC == QPSK_IN_ALAW) return (unsigned)qpsk_alaw_decode(code) & 0xffffu;
+    else return (unsigned)qpsk_ulaw_decode(code) & 0xffffu;
+}
+
+// the block's decode table (QPSK_IN_DEC_TABLE), ready after the next __syncthreads()
+template <int ENC, int DEC>
+__device__ __forceinline__ void fill_table(int16_t* tab) {
+    if constexpr (ENC != QPSK_IN_S16 && DEC == QPSK_IN_DEC_TABLE) {
+        if (threadIdx.x < 256)
+            tab[threadIdx.x] = (int16_t)(ENC == QPSK_IN_ALAW ? qpsk_alaw_decode(threadIdx.x)
+                                                             : qpsk_ulaw_decode(threadIdx.x));
+    }
+}
+
+// 16 codes in 4 dwords -> 16 int16 in 2 x int4
+template <int ENC, int DEC>
+__device__ __forceinline__ void decode16(const unsigned d[4], const int16_t* tab, int16_t* o) {
+    unsigned p[8];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        p[2 * j] = decode<ENC, DEC>(d[j] & 0xffu, tab) | decode<ENC, DEC>((d[j] >> 8) & 0xffu, tab) << 16;
+        p[2 * j + 1] = decode<ENC, DEC>((d[j] >> 16) & 0xffu, tab) | decode<ENC, DEC>(d[j] >> 24, tab) << 16;
+    }
+    uint4* o4 = reinterpret_cast<uint4*>(o);
+    o4[0] = make_uint4(p[0], p[1], p[2], p[3]);
+    o4[1] = make_uint4(p[4], p[5], p[6], p[7]);
+}
+
+// dwords Q .. Q+3 of the 8 in w, taken r bytes further on
+template <int Q>
+__device__ __forceinline__ void shifted(const unsigned w[8], unsigned r, unsigned d[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) d[j] = __builtin_amdgcn_alignbyte(w[Q + j + 1], w[Q + j], r);
+}
+
+template <int ENC, int DEC>
+__global__ __launch_bounds__(kBlock) void planar_kernel(const uint8_t* __restrict__ src,
+                                                        int16_t* __restrict__ out, size_t n) {
+    __shared__ int16_t tab[256];
+    fill_table<ENC, DEC>(tab);
+    __syncthreads();
+    const unsigned a = (unsigned)(reinterpret_cast<uintptr_t>(src) & 15u);   // the call's byte offset
+    const uint4* words = reinterpret_cast<const uint4*>(src - a);
+    const size_t ngroups = (n + 15) / 16;
+    for (size_t g = (size_t)blockIdx.x * kBlock + threadIdx.x; g < ngroups; g += (size_t)gridDim.x * kBlock) {
+        const size_t e0 = g * 16;
+        // word g holds source bytes [e0 - a, e0 - a + 16), word g + 1 the next 16
+        const bool wide = e0 + 16 <= n && (a == 0 || (g > 0 && e0 + 32 - a <= n));
+        if (wide) {
+            const uint4 lo = words[g];
+            const uint4 hi = a ? words[g + 1] : make_uint4(0, 0, 0, 0);
+            const unsigned w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+            unsigned d[4];
+            switch (a >> 2) {   // the same in every lane
+                case 0: shifted<0>(w, a & 3u, d); break;
+                case 1: shifted<1>(w, a & 3u, d); break;
+                case 2: shifted<2>(w, a & 3u, d); break;
+                default: shifted<3>(w, a & 3u, d); break;
+            }
+            decode16<ENC, DEC>(d, tab, out + e0);
+        } else {
+            for (size_t e = e0; e < e0 + 16 && e < n; e++) out[e] = (int16_t)decode<ENC, DEC>(src[e], tab);
+        }
+    }
+}
+
+template <int W> struct LoadOf;
+template <> struct LoadOf<1> { using type = uint8_t; };
+template <> struct LoadOf<2> { using type = uint16_t; };
+template <> struct LoadOf<4> { using type = uint32_t; };
+template <> struct LoadOf<8> { using type = uint2; };
+template <> struct LoadOf<16> { using type = uint4; };
+
+// W bytes at p (W-aligned) as dwords
+template <int W>
+__device__ __forceinline__ void load_wide(const uint8_t* p, unsigned* v) {
+    const auto x = *reinterpret_cast<const typename LoadOf<W>::type*>(p);
+    if constexpr (W == 16) v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
+    else if constexpr (W == 8) v[0] = x.x, v[1] = x.y;
+    else v[0] = x;
+}
+
+template <int ENC, int W, int DEC>
+__global__ __launch_bounds__(kBlock) void interleaved_kernel(const uint8_t* __restrict__ src, size_t ld,
+                                                             unsigned nch, size_t T,
+                                                             int16_t* __restrict__ out, unsigned ctiles,
+                                                             size_t ntiles) {
+    constexpr int ES = ENC == QPSK_IN_S16 ? 2 : 1;   // bytes of an element
+    constexpr int RS = kTC * ES + 4;                 // bytes of a tile row in LDS: one dword of padding
+    constexpr int LPR = kTC * ES / W;                // lanes that load a row
+    constexpr int RPP = kBlock / LPR;                // rows per pass of the block
+    constexpr int NP = kTT / RPP;                    // passes
+    constexpr int V = W / ES;                        // elements of a lane's load
+    constexpr int DW = W >= 4 ? W / 4 : 1;
+    static_assert(W >= ES && LPR >= 1 && RPP <= kTT && NP * RPP == kTT, "tile shape");
+    __shared__ __attribute__((aligned(16))) uint8_t raw[kTT * RS];
+    __shared__ int16_t tab[256];
+    fill_table<ENC, DEC>(tab);
+    const unsigned k = threadIdx.x % LPR, r0 = threadIdx.x / LPR;
+    for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const unsigned c0 = (unsigned)(tile % ctiles) * kTC;
+        const size_t t0 = (tile / ctiles) * kTT;
+        // rows of the source into registers, then into the tile as they are
+        const unsigned cl = c0 + k * V;   // the first channel of this lane's loads
+        unsigned v[NP][DW];
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            const size_t t = t0 + r0 + p * RPP;
+#pragma unroll
+            for (int j = 0; j < DW; j++) v[p][j] = 0;
+            if (t < T && cl < nch) {
+                const uint8_t* row = src + (t * ld + cl) * ES;
+                if (cl + V <= nch) {
+                    load_wide<W>(row, v[p]);
+                } else {   // the tile's last channels: only those there are
+#pragma unroll
+                    for (int j = 0; j < V; j++)
+                        if (cl + j < nch) {
+                            const unsigned x = ES == 1 ? row[j] : reinterpret_cast<const uint16_t*>(row)[j];
+                            v[p][(j * ES) / 4] |= x << (8 * ((j * ES) % 4));
+                        }
+                }
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            const unsigned b = (r0 + p * RPP) * RS + k * W;
+            if constexpr (W >= 4) {
+#pragma unroll
+                for (int j = 0; j < DW; j++) reinterpret_cast<unsigned*>(raw)[b / 4 + j] = v[p][j];
+            } else if constexpr (W == 2) {
+                *reinterpret_cast<uint16_t*>(raw + b) = (uint16_t)v[p][0];
+            } else {
+                raw[b] = (uint8_t)v[p][0];
+            }
+        }
+        __syncthreads();
+        // a lane: 8 samples of one channel down the rows -> 16 bytes along time
+#pragma unroll
+        for (int it = 0; it < kTC * (kTT / 8) / kBlock; it++) {
+            const unsigned s = threadIdx.x + it * kBlock;
+            const unsigned c = (s % 8) + 8 * (s / 128), tq = (s / 8) % (kTT / 8);
+            const size_t t = t0 + tq * 8;
+            if (c0 + c < nch && t < T) {   // T is a multiple of 8: all 8 samples or none
+                unsigned x[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const unsigned b = (tq * 8 + i) * RS + c * ES;
+                    const unsigned code = ES == 1 ? raw[b] : *reinterpret_cast<const uint16_t*>(raw + b);
+                    x[i] = decode<ENC, DEC>(code, tab);
+                }
+                *reinterpret_cast<uint4*>(out + (size_t)(c0 + c) * T + t) =
+                    make_uint4(x[0] | x[1] << 16, x[2] | x[3] << 16, x[4] | x[5] << 16, x[6] | x[7] << 16);
+            }
+        }
+        __syncthreads();   // the tile is rewritten by the next round
+    }
+}
+
+unsigned grid_of(size_t blocks) { return (unsigned)(blocks < kMaxGrid ? blocks : kMaxGrid); }
+
+template <int ENC, int DEC>
+void launch_planar(const uint8_t* src, int16_t* out, size_t n, hipStream_t s) {
+    const size_t groups = (n + 15) / 16;
+    hipLaunchKernelGGL((planar_kernel<ENC, DEC>), dim3(grid_of((groups + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                       src, out, n);
+}
+
+template <int ENC, int W, int DEC>
+void launch_tile(const uint8_t* src, size_t ld, unsigned nch, size_t T, int16_t* out, hipStream_t s) {
+    const unsigned ctiles = (nch + kTC - 1) / kTC;
+    const size_t ntiles = (size_t)ctiles * ((T + kTT - 1) / kTT);
+    hipLaunchKernelGGL((interleaved_kernel<ENC, W, DEC>), dim3(grid_of(ntiles)), dim3(kBlock), 0, s, src, ld, nch, T,
+                       out, ctiles, ntiles);
+}
+
+template <int ENC, int DEC>
+void launch_interleaved(int w, const uint8_t* src, size_t ld, unsigned nch, size_t T, int16_t* out, hipStream_t s) {
+    switch (w) {
+        case 16: return launch_tile<ENC, 16, DEC>(src, ld, nch, T, out, s);
+        case 8: return launch_tile<ENC, 8, DEC>(src, ld, nch, T, out, s);
+        case 4: return launch_tile<ENC, 4, DEC>(src, ld, nch, T, out, s);
+        case 2: return launch_tile<ENC, 2, DEC>(src, ld, nch, T, out, s);
+        default:
+            if constexpr (ENC != QPSK_IN_S16) launch_tile<ENC, 1, DEC>(src, ld, nch, T, out, s);
+            return;
+    }
+}
+
+}  // namespace
+
+// The widest load every row of an interleaved block allows: a tile's rows start
+// at src + (t * ld + 64 * i) * esize, so the address of the block and the byte
+// stride of its rows decide for the whole call.
+extern "C" int qpsk_input_load_width(const void* d_src, long ld, int esize) {
+    const uintptr_t m = reinterpret_cast<uintptr_t>(d_src) | (uintptr_t)ld * (uintptr_t)esize;
+    int w = 16;
+    while (w > esize && (m & (uintptr_t)(w - 1)) != 0) w >>= 1;
+    return w;
+}
+
+extern "C" int qpsk_input_convert_device_dec(int fmt, const void* d_src, long ld, int nch, int nframes,
+                                             int16_t* d_out, void* stream, int dec) {
+    if (qpsk_input_check(fmt, nch, nframes, ld) != QPSK_OK) return QPSK_EINVAL;
+    if (dec == QPSK_IN_DEC_DEFAULT)
+        dec = QPSK_IN_LAYOUT(fmt) == QPSK_IN_PLANAR ? QPSK_IN_DEC_TABLE : QPSK_IN_DEC_ARITH;
+    if (dec != QPSK_IN_DEC_ARITH && dec != QPSK_IN_DEC_TABLE) return QPSK_EINVAL;
+    if (nframes == 0) return QPSK_OK;
+    const int es = qpsk_input_esize(fmt), enc = QPSK_IN_ENC(fmt);
+    if (!d_src || !d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_src) & (uintptr_t)(es - 1)) != 0)
+        return QPSK_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const uint8_t* src = static_cast<const uint8_t*>(d_src);
+    const size_t T = (size_t)nframes * QK_FRAME, n = (size_t)nch * T;
+    const bool table = dec == QPSK_IN_DEC_TABLE;
+    if (QPSK_IN_LAYOUT(fmt) == QPSK_IN_PLANAR) {
+        if (enc == QPSK_IN_S16) {
+            HCHECK(hipMemcpyAsync(d_out, d_src, n * sizeof(int16_t), hipMemcpyDeviceToDevice, s));
+            return QPSK_OK;
+        }
+        if (enc == QPSK_IN_ALAW) {
+            if (table) launch_planar<QPSK_IN_ALAW, QPSK_IN_DEC_TABLE>(src, d_out, n, s);
+            else launch_planar<QPSK_IN_ALAW, QPSK_IN_DEC_ARITH>(src, d_out, n, s);
+        } else {
+            if (table) launch_planar<QPSK_IN_ULAW, QPSK_IN_DEC_TABLE>(src, d_out, n, s);
+            else launch_planar<QPSK_IN_ULAW, QPSK_IN_DEC_ARITH>(src, d_out, n, s);
+        }
+    } else {
+        const int w = qpsk_input_load_width(d_src, ld, es);
+        const unsigned uc = (unsigned)nch;
+        if (enc == QPSK_IN_S16) {
+            launch_interleaved<QPSK_IN_S16, QPSK_IN_DEC_ARITH>(w, src, (size_t)ld, uc, T, d_out, s);
+        } else if (enc == QPSK_IN_ALAW) {
+            if (table) launch_interleaved<QPSK_IN_ALAW, QPSK_IN_DEC_TABLE>(w, src, (size_t)ld, uc, T, d_out, s);
+            else launch_interleaved<QPSK_IN_ALAW, QPSK_IN_DEC_ARITH>(w, src, (size_t)ld, uc, T, d_out, s);
+        } else {
+            if (table) launch_interleaved<QPSK_IN_ULAW, QPSK_IN_DEC_TABLE>(w, src, (size_t)ld, uc, T, d_out, s);
+            else launch_interleaved<QPSK_IN_ULAW, QPSK_IN_DEC_ARITH>(w, src, (size_t)ld, uc, T, d_out, s);
+        }
+    }
+    HCHECK(hipGetLastError());
+    return QPSK_OK;
+}
+
+extern "C" int qpsk_input_convert_device(int fmt, const void* d_src, long ld, int nch, int nframes,
+                                         int16_t* d_out, void* stream) {
+    return qpsk_input_convert_device_dec(fmt, d_src, ld, nch, nframes, d_out, stream, QPSK_IN_DEC_DEFAULT);
+}
+
+// ---------------------------------------------------------------- the receive path behind it
+namespace {
+
+struct HostFeed {
+    qpsk_ctx* c;
+    const void* in;
+    int fmt, nch, F;
+    long ld;
+};
+
+// the source block over PCIe as it is, then converted into the staging block's input
+int feed_fmt(void* arg, int16_t* d_in, hipStream_t s) {
+    const HostFeed* f = static_cast<const HostFeed*>(arg);
+    const size_t nraw = qpsk_input_bytes(f->fmt, f->nch, f->F, f->ld);
+    char* raw = nullptr;
+    const int r = qpsk_rx_fmt_raw(f->c, nraw, &raw);
+    if (r != QPSK_OK) return r;
+    HCHECK(hipMemcpyAsync(raw, f->in, nraw, hipMemcpyHostToDevice, s));
+    return qpsk_input_convert_device(f->fmt, raw, f->ld, f->nch, f->F, d_in, s);
+}
+
+}  // namespace
+
+extern "C" int qpsk_rx_batch_fmt(qpsk_ctx* c, const void* in, int fmt, long ld, int F, uint8_t* bits,
+                                 uint8_t* valid, int32_t* trace, float* soft) {
+    if (fmt == (QPSK_IN_S16 | QPSK_IN_PLANAR))
+        return qpsk_rx_batch(c, static_cast<const int16_t*>(in), F, bits, valid, trace, soft);
+    const int nch = qpsk_rx_channels(c);   // 0 for a null context
+    if (qpsk_input_check(fmt, nch, F, ld) != QPSK_OK || (F > 0 && !in)) return QPSK_EINVAL;
+    HostFeed f{c, in, fmt, nch, F, ld};
+    return qpsk_rx_batch_fed(c, feed_fmt, &f, F, bits, valid, trace, soft);
+}
+
+extern "C" int qpsk_rx_batch_device_fmt(qpsk_ctx* c, const void* d_in, int fmt, long ld, int F,
+                                        uint8_t* d_bits, uint8_t* d_valid, int32_t* d_trace,
+                                        float* d_soft, void* stream) {
+    if (fmt == (QPSK_IN_S16 | QPSK_IN_PLANAR))
+        return qpsk_rx_batch_device(c, static_cast<const int16_t*>(d_in), F, d_bits, d_valid, d_trace, d_soft, stream);
+    const int nch = qpsk_rx_channels(c);
+    if (qpsk_input_check(fmt, nch, F, ld) != QPSK_OK || (F > 0 && (!d_in || !d_bits || !d_valid)))
+        return QPSK_EINVAL;
+    if (F == 0) return qpsk_rx_batch_device(c, nullptr, 0, d_bits, d_valid, d_trace, d_soft, stream);
+    int16_t* conv = nullptr;
+    int r = qpsk_rx_fmt_conv(c, (size_t)nch * (size_t)F * QK_FRAME, &conv);
+    if (r != QPSK_OK) return r;
+    r = qpsk_input_convert_device(fmt, d_in, ld, nch, F, conv, stream);
+    if (r != QPSK_OK) return r;
+    return qpsk_rx_batch_device(c, conv, F, d_bits, d_valid, d_trace, d_soft, stream);
+}
+
+extern "C" qpsk_stream* qpsk_stream_create_fmt(int device, int nch, int frames, int nslot, int mode, int fmt,
+                                               int* err) {
+    if (fmt == (QPSK_IN_S16 | QPSK_IN_PLANAR)) return qpsk_stream_create_mode(device, nch, frames, nslot, mode, err);
+    if (frames < 1 || qpsk_input_check(fmt, nch, frames, nch) != QPSK_OK) {
+        if (err) *err = QPSK_EINVAL;
+        return nullptr;
+    }
+    return qpsk_stream_create_raw(device, nch, frames, nslot, mode, fmt, qpsk_input_bytes(fmt, nch, frames, nch),
+                                  qpsk_input_convert_device, err);
+}

@@ -172,6 +172,15 @@ struct Staging {
     }
 };
 
+// input in another format than planar int16 (include/qpsk_input.h, built in
+// qpsk_input.hip on qpsk_rx_fmt_raw / qpsk_rx_fmt_conv): the source block as
+// it crossed PCIe (qpsk_rx_batch_fmt) and the converted block of device calls
+// (qpsk_rx_batch_device_fmt).  Empty until such a call.
+struct FmtInput {
+    qhip::DevBuf<char> raw;
+    qhip::DevBuf<int16_t> conv;
+};
+
 // kernel-span accounting: events before rx_kernel, between the kernels, after
 // rx_data_kernel, from a pool that is folded into running sums when it is full
 struct SpanTimer {
@@ -248,6 +257,7 @@ struct qpsk_ctx {
     ChanState st;
     JobQueue q;
     Staging stage;
+    FmtInput fmt;
     SpanTimer spans;
     RxKnobs knobs;
     Assembly assembly;
@@ -634,9 +644,13 @@ extern "C" int qpsk_rx_timing_collect(qpsk_ctx* c, float* ms, int* frames) {
     return r;
 }
 
-extern "C" int qpsk_rx_batch(qpsk_ctx* c, const int16_t* in, int F, uint8_t* bits, uint8_t* valid,
-                             int32_t* trace, float* soft) {
-    if (!c || F < 0 || (F > 0 && (!in || !bits || !valid))) return QPSK_EINVAL;
+// qpsk_rx_batch (feed == nullptr: `in` goes to the staging block as it is) and
+// qpsk_rx_batch_fed (`feed` fills the staging block's input on the context's
+// stream, qpsk_rx_internal.h)
+static int rx_batch_host(qpsk_ctx* c, const int16_t* in, qpsk_rx_feed_fn feed, void* arg, int F, uint8_t* bits,
+                         uint8_t* valid, int32_t* trace, float* soft) {
+    const bool plain = feed == nullptr;
+    if (!c || F < 0 || (F > 0 && ((plain && !in) || !bits || !valid))) return QPSK_EINVAL;
     if (c->assembly.left > 0) return QPSK_EINVAL;   // channels not yet loaded (qpsk_rx_state_load)
     if (F == 0) return QPSK_OK;
     HCHECK(hipSetDevice(c->device));
@@ -666,8 +680,8 @@ extern "C" int qpsk_rx_batch(qpsk_ctx* c, const int16_t* in, int F, uint8_t* bit
         if (*h.err() != 0) c->stalled = true;
         return *h.err() != 0 ? QPSK_ESTALL : QPSK_OK;
     };
-    if (pin) memcpy(h.in(), in, nin);
-    if (pin && cf <= kZeroCopyCF) {
+    if (pin && plain) memcpy(h.in(), in, nin);
+    if (pin && plain && cf <= kZeroCopyCF) {
         // tiny calls: the kernels read the input from and write the outputs to
         // the pinned block directly (device-accessible host memory); the
         // per-frame latency is then two launches and one synchronisation, not
@@ -677,7 +691,12 @@ extern "C" int qpsk_rx_batch(qpsk_ctx* c, const int16_t* in, int F, uint8_t* bit
         HCHECK(hipStreamSynchronize(c->stream));
         return finish();
     }
-    HCHECK(hipMemcpyAsync(d.in(), pin ? (const void*)h.in() : (const void*)in, nin, hipMemcpyHostToDevice, c->stream));
+    if (plain) {
+        HCHECK(hipMemcpyAsync(d.in(), pin ? (const void*)h.in() : (const void*)in, nin, hipMemcpyHostToDevice, c->stream));
+    } else {
+        r = feed(arg, d.in(), c->stream);
+        if (r != QPSK_OK) return r;
+    }
     // pinned: the error word is taken by rx_data_kernel (err_to) into the
     // staging block right after the valid flags, so bits, flags and error word
     // come back in one copy; pageable: qpsk_rx_sync() takes it
@@ -699,6 +718,36 @@ extern "C" int qpsk_rx_batch(qpsk_ctx* c, const int16_t* in, int F, uint8_t* bit
     if (soft) HCHECK(hipMemcpyAsync(h.soft(), d.soft(), nso, hipMemcpyDeviceToHost, c->stream));
     HCHECK(hipStreamSynchronize(c->stream));
     return finish();
+}
+
+extern "C" int qpsk_rx_batch(qpsk_ctx* c, const int16_t* in, int F, uint8_t* bits, uint8_t* valid,
+                             int32_t* trace, float* soft) {
+    return rx_batch_host(c, in, nullptr, nullptr, F, bits, valid, trace, soft);
+}
+
+int qpsk_rx_batch_fed(qpsk_ctx* c, qpsk_rx_feed_fn feed, void* arg, int F, uint8_t* bits, uint8_t* valid,
+                      int32_t* trace, float* soft) {
+    if (!feed) return QPSK_EINVAL;
+    return rx_batch_host(c, nullptr, feed, arg, F, bits, valid, trace, soft);
+}
+
+int qpsk_rx_fmt_raw(qpsk_ctx* c, size_t bytes, char** p) {
+    if (!c || !p) return QPSK_EINVAL;
+    HCHECK(hipSetDevice(c->device));
+    HCHECK(c->fmt.raw.reserve(bytes));
+    *p = c->fmt.raw;
+    return QPSK_OK;
+}
+
+int qpsk_rx_fmt_conv(qpsk_ctx* c, size_t n, int16_t** p) {
+    if (!c || !p) return QPSK_EINVAL;
+    HCHECK(hipSetDevice(c->device));
+    if (n > c->fmt.conv.cap()) {
+        HCHECK(hipDeviceSynchronize());   // an earlier call may still read the block
+        HCHECK(c->fmt.conv.reserve(n));
+    }
+    *p = c->fmt.conv;
+    return QPSK_OK;
 }
 
 extern "C" const char* qpsk_strerror(int err) {

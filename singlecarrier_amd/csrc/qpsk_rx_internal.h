@@ -25,6 +25,33 @@ uint64_t qpsk_rx_epoch(const qpsk_ctx* c);
 // context's per-channel state is undefined (qpsk_rx_state_save refuses it).
 void qpsk_rx_mark_stalled(qpsk_ctx* c, uint64_t epoch);
 
+// Input in another format than planar int16 (include/qpsk_input.h).  The
+// receive path and the streams know nothing of formats: qpsk_input.hip, which
+// has the conversions, builds the format entry points on the three hooks below,
+// and neither qpsk_rx_host.hip nor qpsk_stream.hip refers to a symbol of it.
+//
+// qpsk_rx_batch() whose input is made on the device: after the staging block
+// is ready, `feed` enqueues on s whatever writes int16 [nch][F][1880] to d_in
+// (the block's input), in place of the copy of a host array.
+typedef int (*qpsk_rx_feed_fn)(void* arg, int16_t* d_in, hipStream_t s);
+int qpsk_rx_batch_fed(qpsk_ctx* c, qpsk_rx_feed_fn feed, void* arg, int F, uint8_t* bits, uint8_t* valid,
+                      int32_t* trace, float* soft);
+// Grow-only device buffers of the context: the source block of a host call as
+// it crossed PCIe (the caller has synchronised its previous use: every host
+// call does), and the converted block of device calls (a call larger than
+// every earlier one waits for the device before the buffer is reallocated).
+int qpsk_rx_fmt_raw(qpsk_ctx* c, size_t bytes, char** p);
+int qpsk_rx_fmt_conv(qpsk_ctx* c, size_t n, int16_t** p);
+// qpsk_stream_create_mode() for chunks that are source blocks of raw_bytes
+// bytes in format fmt: a slot's pinned input is such a block, and submit runs
+// `convert` (the signature of qpsk_input_convert_device, ld = nch) on the
+// receive stream in front of the receive.  convert == nullptr: a plain stream.
+typedef int (*qpsk_convert_fn)(int fmt, const void* d_src, long ld, int nch, int nframes, int16_t* d_out,
+                               void* stream);
+struct qpsk_stream;
+qpsk_stream* qpsk_stream_create_raw(int device, int nch, int frames, int nslot, int mode, int fmt,
+                                    size_t raw_bytes, qpsk_convert_fn convert, int* err);
+
 // The stream that owns a context (qpsk_stream_create_mode): qpsk_rx_reset()
 // and qpsk_rx_state_load() refuse with QPSK_EBUSY while it has chunks pending.
 struct qpsk_stream;

@@ -21,6 +21,10 @@ constexpr int kMaxSlots = 4;
 struct Slot {
     qhip::PinBuf<int16_t> h_in;
     qhip::DevBuf<int16_t> d_in;
+    // a stream of another input format (qpsk_stream_create_fmt): the source
+    // block, pinned and on the device, in place of h_in; d_in is converted from it
+    qhip::PinBuf<char> h_raw;
+    qhip::DevBuf<char> d_raw;
     qhip::DevBuf<uint8_t> d_bits, d_valid;
     qhip::PinBuf<uint8_t> h_bits, h_valid;
     qhip::DevBuf<int> d_err;     // the chunk's device error word (progress-wait stalls)
@@ -38,6 +42,12 @@ __global__ void err_merge_kernel(int* ctx_err, const int* slot_err) {
 
 struct qpsk_stream {
     int device = 0, nch = 0, frames = 0, nslot = 0;
+    // chunks in another input format than planar int16 (qpsk_stream_create_raw):
+    // the format word, the bytes of a chunk's source block and the conversion
+    int fmt = 0;
+    size_t raw_bytes = 0;
+    qpsk_convert_fn convert = nullptr;
+    bool plain() const { return convert == nullptr; }
     // released in reverse order: the slots, the streams, then the receiver
     struct RxDestroy {
         void operator()(qpsk_ctx* c) const { qpsk_rx_destroy(c); }
@@ -63,7 +73,12 @@ static int stream_alloc(qpsk_stream* s) {
     const size_t cf = (size_t)s->nch * (size_t)s->frames;
     for (int i = 0; i < s->nslot; i++) {
         Slot& q = s->slot[i];
-        HCHECK(q.h_in.reserve(cf * QK_FRAME));
+        if (s->plain()) {
+            HCHECK(q.h_in.reserve(cf * QK_FRAME));
+        } else {
+            HCHECK(q.h_raw.reserve(s->raw_bytes));
+            HCHECK(q.d_raw.reserve(s->raw_bytes));
+        }
         HCHECK(q.h_bits.reserve(cf * QK_NBITS));
         HCHECK(q.h_valid.reserve(cf));
         HCHECK(q.d_in.reserve(cf * QK_FRAME));
@@ -84,13 +99,22 @@ extern "C" qpsk_stream* qpsk_stream_create(int device, int nch, int frames, int 
 
 extern "C" qpsk_stream* qpsk_stream_create_mode(int device, int nch, int frames, int nslot,
                                                 int mode, int* err) {
+    return qpsk_stream_create_raw(device, nch, frames, nslot, mode, 0, 0, nullptr, err);
+}
+
+qpsk_stream* qpsk_stream_create_raw(int device, int nch, int frames, int nslot, int mode, int fmt,
+                                    size_t raw_bytes, qpsk_convert_fn convert, int* err) {
     if (nch < 1 || frames < 1 || nslot < 1 || nslot > kMaxSlots) return qhip::fail(err, QPSK_EINVAL);
+    if (convert && raw_bytes == 0) return qhip::fail(err, QPSK_EINVAL);
     qpsk_stream* s = new (std::nothrow) qpsk_stream();
     if (!s) return qhip::fail(err, QPSK_ENOMEM);
     s->device = device;
     s->nch = nch;
     s->frames = frames;
     s->nslot = nslot;
+    s->fmt = fmt;
+    s->raw_bytes = raw_bytes;
+    s->convert = convert;
     int r = QPSK_OK;
     s->rx.reset(qpsk_rx_create_mode(device, nch, mode, &r));
     if (s->rx) {
@@ -114,17 +138,30 @@ extern "C" void qpsk_stream_destroy(qpsk_stream* s) {
     delete s;
 }
 
-extern "C" int16_t* qpsk_stream_acquire(qpsk_stream* s, int* err) {
-    if (!s) return qhip::fail(err, QPSK_EINVAL);
+// the slot of the next chunk, or nullptr (*err = QPSK_EBUSY)
+static Slot* acquire_slot(qpsk_stream* s, int* err) {
     if (s->acquired != s->submitted) {   // acquired twice without a submit
         qhip::set_err(err, QPSK_OK);
-        return s->slot[s->acquired % (uint64_t)s->nslot].h_in;
+        return &s->slot[s->acquired % (uint64_t)s->nslot];
     }
     // the slot's previous chunk must have been retrieved (its outputs and its
     // input buffer are the caller's until then)
     if (s->acquired - s->retrieved >= (uint64_t)s->nslot) return qhip::fail(err, QPSK_EBUSY);
     qhip::set_err(err, QPSK_OK);
-    return s->slot[s->acquired++ % (uint64_t)s->nslot].h_in;
+    return &s->slot[s->acquired++ % (uint64_t)s->nslot];
+}
+
+extern "C" int16_t* qpsk_stream_acquire(qpsk_stream* s, int* err) {
+    if (!s || !s->plain()) return qhip::fail(err, QPSK_EINVAL);
+    Slot* q = acquire_slot(s, err);
+    return q ? q->h_in.get() : nullptr;
+}
+
+extern "C" void* qpsk_stream_acquire_raw(qpsk_stream* s, int* err) {
+    if (!s) return qhip::fail(err, QPSK_EINVAL);
+    Slot* q = acquire_slot(s, err);
+    if (!q) return nullptr;
+    return s->plain() ? static_cast<void*>(q->h_in.get()) : static_cast<void*>(q->h_raw.get());
 }
 
 extern "C" int qpsk_stream_submit(qpsk_stream* s) {
@@ -132,10 +169,17 @@ extern "C" int qpsk_stream_submit(qpsk_stream* s) {
     Slot& q = s->slot[s->submitted % (uint64_t)s->nslot];
     const size_t cf = (size_t)s->nch * (size_t)s->frames;
     HCHECK(hipSetDevice(s->device));
-    HCHECK(hipMemcpyAsync(q.d_in, q.h_in, sizeof(int16_t) * cf * QK_FRAME, hipMemcpyHostToDevice,
-                          s->s_h2d));
+    if (s->plain())
+        HCHECK(hipMemcpyAsync(q.d_in, q.h_in, sizeof(int16_t) * cf * QK_FRAME, hipMemcpyHostToDevice,
+                              s->s_h2d));
+    else
+        HCHECK(hipMemcpyAsync(q.d_raw, q.h_raw, s->raw_bytes, hipMemcpyHostToDevice, s->s_h2d));
     HCHECK(hipEventRecord(q.copied, s->s_h2d));
     HCHECK(hipStreamWaitEvent(s->s_rx, q.copied, 0));
+    if (!s->plain()) {   // the narrow block -> int16 [nch][frames][1880], in front of the receive
+        const int cr = s->convert(s->fmt, q.d_raw, s->nch, s->nch, s->frames, q.d_in, s->s_rx);
+        if (cr != QPSK_OK) return cr;
+    }
     HCHECK(hipMemsetAsync(q.d_err, 0, sizeof(int), s->s_rx));
     const int r = qpsk_rx_launch(s->rx.get(), q.d_in, s->frames, q.d_bits, q.d_valid, nullptr, nullptr,
                                  s->s_rx, q.d_err);
