@@ -376,8 +376,6 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, DUAL, W, QUAD>),
             }
 #undef QPSK_DUAL_FRONT_FRAME
             STAMP_FLUSH();
-            for (int bb = 0; bb < kChainWaves; bb++)
-                carry_history<DM>(a.in, a.hist, a.F, bch0(bb), blive(bb), lane);
         }
         __syncthreads();
         if (wave < kBackWaves && (wave & 1) == 0) {   // state after the call's last frame
@@ -483,7 +481,6 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, DUAL, W, QUAD>),
             STAMP(7);
         }
         STAMP_FLUSH();
-        carry_history<DM>(a.in, a.hist, a.F, ch0, nlive, lane);
     }
 }
 
@@ -587,10 +584,16 @@ int qpsk_rx_launch_kernels(const RxLaunch& a) {
     // qpsk_rx_frame is one job at most) launches only the workgroups it can use
     const size_t need = (size_t)a.nch * (size_t)a.F;
     const unsigned dgrid = (unsigned)std::min<size_t>(kDataGrid, (need + kDataBlock - 1) / kDataBlock);
-    hipLaunchKernelGGL(rx_data_kernel, dim3(dgrid), dim3(kDataBlock), 0, a.s, a.jobs,
+    // in front of them the workgroups that carry the sample history (carry_block):
+    // one batch of kCarryK channels per wave up to kCarryGrid workgroups, so a
+    // one-channel call gets one
+    constexpr int kPerBlock = kDataBlock / 64 * kCarryK;
+    const unsigned ncarry = (unsigned)std::min(kCarryGrid, (a.nch + kPerBlock - 1) / kPerBlock);
+    const int head8 = (a.mode & QPSK_MODE_DEC752) ? 213 : 149;   // x_{F-1}[0..1704) or [0..1192)
+    hipLaunchKernelGGL(rx_data_kernel, dim3(ncarry + dgrid), dim3(kDataBlock), 0, a.s, a.jobs,
                        (unsigned long long)a.jobs_cap, a.njobs, a.ks, a.bits,
                        reinterpret_cast<float2*>(a.soft), a.parity, a.roles & kForceExact, a.ctx_err,
-                       a.err_to);
+                       a.err_to, a.in, a.hist, a.nch, a.F, head8, ncarry);
     HCHECK(hipGetLastError());
     if (a.ev_end) HCHECK(hipEventRecord(a.ev_end, a.s));
     return QPSK_OK;

@@ -388,6 +388,62 @@ __device__ __forceinline__ unsigned long long data_steps(Kal& k, f2 (&x)[5], con
     return dib;
 }
 
+// ---------------------------------------------------------------- history carry
+// The samples the next call needs, from the call's input into the context's
+// history [nch][2][1880] (h0, h1): x_{F-1}[0..8 head8) and x_{F-1}[1832..1879]
+// into h1, x_{F-2}[1832..1879] into h0; head8 = 149 (1192 samples), or 213
+// (1704) in the dec752 mode.  One channel is 16-B units u < head8 + 12, four
+// per lane: u < head8 the head, the next 6 h1's tail, the last 6 h0's.
+// A wave takes kCarryK channels at a time and waves stride over the channels;
+// it issues the loads of all of them before the first store, so each wave keeps
+// kCarryK x 4 KB in flight.  A one-frame call's x_{F-2} tail is what h1 holds:
+// that load precedes the wave's stores to h1, and no other wave writes the
+// channel.
+constexpr int kCarryK = 4;       // channels per wave in flight
+constexpr int kCarryGrid = 256;  // carry workgroups at most (profiles/carry_data_launch_ab.txt)
+
+typedef int carry_v4 __attribute__((ext_vector_type(4)));   // (an int4 array stays in scratch)
+__device__ __forceinline__ void carry_block(const int16_t* in, int16_t* hist, int nch, int F, int head8,
+                                            int wave, int nwaves, int lane) {
+    const int nunit = head8 + 12;
+    for (int c0 = wave * kCarryK; c0 < nch; c0 += nwaves * kCarryK) {
+        carry_v4 v[kCarryK][4];
+#pragma unroll
+        for (int k = 0; k < kCarryK; k++) {
+            // (a lane past the batch's channels or the channel's units loads the
+            // last one's again and stores nothing: every load is unconditional)
+            const int ch = min(c0 + k, nch - 1);
+            const int16_t* h1 = hist + ((size_t)ch * 2 + 1) * QK_FRAME;
+            const int16_t* last = in + ((size_t)ch * F + (F - 1)) * QK_FRAME;
+            const int16_t* prev = F >= 2 ? last - QK_FRAME : h1;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int u = min(lane + 64 * j, nunit - 1);
+                const int16_t* src = u < head8       ? last + 8 * u
+                                     : u < head8 + 6 ? last + 1832 + 8 * (u - head8)
+                                                     : prev + 1832 + 8 * (u - head8 - 6);
+                v[k][j] = *reinterpret_cast<const carry_v4*>(src);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kCarryK; k++) {
+            const int ch = c0 + k;
+            int16_t* h0 = hist + (size_t)ch * 2 * QK_FRAME;
+            int16_t* h1 = h0 + QK_FRAME;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int u = lane + 64 * j;
+                if (ch < nch && u < nunit) {
+                    int16_t* dst = u < head8       ? h1 + 8 * u
+                                   : u < head8 + 6 ? h1 + 1832 + 8 * (u - head8)
+                                                   : h0 + 1832 + 8 * (u - head8 - 6);
+                    *reinterpret_cast<carry_v4*>(dst) = v[k][j];
+                }
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- data kernel
 // The 31 data symbols of every valid frame (src/qpsk.c:204-215: data_eq
 // src/equalizer.c:64-90, qpsk_demod src/qpsk.c:268-271, scramble
@@ -396,19 +452,39 @@ __device__ __forceinline__ unsigned long long data_steps(Kal& k, f2 (&x)[5], con
 // lanes for 31 of its 159 steps.  Jobs come from the call's rx_kernel in any
 // order; every output location is fixed by the job, so results do not depend
 // on it.
+// The launch's first ncarry workgroups carry the sample history instead
+// (carry_block): the jobs keep the VALU busy and leave the memory system
+// nearly idle, so the copy runs beside them.  The call's rx_kernel, which reads
+// the history for its first frame, is done (stream order), and the next
+// call's comes after this launch.
 __global__ void __launch_bounds__(256) rx_data_kernel(const float4* jobs, unsigned long long jcap,
                                                       unsigned* njobs,
                                                       const unsigned long long* ks_tab,
                                                       uint8_t* bits, float2* soft, int parity,
-                                                      int force_exact, int* err, int* err_to) {
-    // err_to (host calls, qpsk_rx_batch): the context's error word, taken in one
-    // atomic exchange after rx_kernel (stream order), stored with the outputs:
-    // no separate launch for it
-    if (err_to && blockIdx.x == 0 && threadIdx.x == 0) *err_to = atomicExch(err, 0);
+                                                      int force_exact, int* err, int* err_to,
+                                                      const int16_t* in, int16_t* hist, int nch, int F,
+                                                      int head8, unsigned ncarry) {
+    if (blockIdx.x < ncarry) {
+        // ncarry >= 1, so workgroup 0 always carries; its first thread has the
+        // launch's two single-thread duties (on a job workgroup's they keep the
+        // job index live over the loop: 15 spilled SGPRs and a 159th VGPR)
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            // err_to (host calls, qpsk_rx_batch): the context's error word, taken in one
+            // atomic exchange after rx_kernel (stream order), stored with the outputs:
+            // no separate launch for it
+            if (err_to) *err_to = atomicExch(err, 0);
+            // the next call's counter (calls on one context are stream-ordered)
+            njobs[parity ^ 1] = 0u;
+        }
+        carry_block(in, hist, nch, F, head8, (int)(blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64),
+                    (int)(ncarry * (blockDim.x / 64)), lane_id());
+        return;
+    }
+    // the job workgroups follow the carry workgroups
     const size_t cap = (size_t)jcap;
     const unsigned n = njobs[parity];
-    const unsigned stride = gridDim.x * blockDim.x;
-    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const unsigned stride = (gridDim.x - ncarry) * blockDim.x;
+    for (unsigned i = (blockIdx.x - ncarry) * blockDim.x + threadIdx.x; i < n; i += stride) {
         const unsigned off = i * (unsigned)sizeof(float4);
         DataJob j;
         get_job(jobs, cap, off, j);
@@ -432,7 +508,5 @@ __global__ void __launch_bounds__(256) rx_data_kernel(const float4* jobs, unsign
         for (int q = 0; q < QK_NDSYM; q++)
             bo[q] = (uint16_t)(((dib >> (2 * q)) & 1ull) | (((dib >> (2 * q + 1)) & 1ull) << 8));
     }
-    // the next call's counter (calls on one context are stream-ordered)
-    if (blockIdx.x == 0 && threadIdx.x == 0) njobs[parity ^ 1] = 0u;
 }
 }  // namespace

@@ -1,5 +1,5 @@
 // qpsk_rx_front.h -- the front wave of the receive kernels: prefetch, mixer,
-// the three FIRs, the preamble hunt, the window store and history carry, and
+// the three FIRs, the preamble hunt, the window store, and
 // the head pre-pass kernel (included by qpsk_rx.hip only).
 #pragma once
 
@@ -521,28 +521,6 @@ __device__ __forceinline__ void store_window(int lane, int mi, const float2* dec
         const int q = lane + 64;
         const float2 lo = dec[mi + 2 * q - 1], hi = dec[mi + 2 * q];
         o[q] = make_float4(lo.x, lo.y, hi.x, hi.y);
-    }
-}
-
-// carry the samples the next call needs: x_{F-1}[0..hi), x_{F-1}[1832..1879],
-// x_{F-2}[1832..1879]; hi = 1192 (MODE 0) or 1704 (MODE 1), in 8-sample units
-template <int MODE>
-__device__ __forceinline__ void carry_history(const int16_t* in, int16_t* hist, int F, int ch0, int nlive, int lane) {
-    constexpr int kHead8 = MODE == 1 ? 213 : 149;
-    for (int c = 0; c < nlive; c++) {
-        const int ch = ch0 + c;
-        int16_t* h0 = hist + (size_t)ch * 2 * QK_FRAME;
-        int16_t* h1 = h0 + QK_FRAME;
-        const int16_t* last = F >= 1 ? in + ((size_t)ch * F + (F - 1)) * QK_FRAME : h1;
-        const int16_t* prev = F >= 2 ? in + ((size_t)ch * F + (F - 2)) * QK_FRAME : h1;
-        if (lane < 6) {   // F == 1: prev is h1; its load completes before the h1 stores
-            const int t = 1832 + 8 * lane;
-            *reinterpret_cast<int4*>(h0 + t) = *reinterpret_cast<const int4*>(prev + t);
-        }
-        for (int u = lane; u < kHead8 + 6; u += 64) {
-            const int t = u < kHead8 ? 8 * u : 1832 + 8 * (u - kHead8);
-            *reinterpret_cast<int4*>(h1 + t) = *reinterpret_cast<const int4*>(last + t);
-        }
     }
 }
 

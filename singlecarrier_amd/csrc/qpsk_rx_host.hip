@@ -81,7 +81,7 @@ namespace {
 // The state the kernels carry from one call to the next, per channel slot (ns
 // of them, rx_nslot), and the constant tables beside it.  For frame index G
 // (the next frame): the history int16 [2][1880] (frames G-2, G-1:
-// carry_history), window G's row float2 [168] with mi_G, and rt_G, the last
+// carry_block), window G's row float2 [168] with mi_G, and rt_G, the last
 // three in the arrays of parity G & 1 (rx_kernel reads mi_of / rt_of / win_of
 // (g0) at a call's start and writes parity g0 + F at its end).
 struct ChanState {

@@ -26,8 +26,9 @@ constexpr int kErrStall = 1;                // device error word bits
 // front stagger, 512-cycle units (roles bits 8-15): round 1 measured 12 as
 // -0.7%; on round 5's kernels 0 is -0.4% (profiles/r05_stagger_ab.txt)
 constexpr int kStagger = 0;
-// rx_data_kernel grid: persistent, 4 workgroups of 256 per CU (other geometries
-// measured within 2%, profiles/r01_data_ab.txt)
+// rx_data_kernel's job grid: persistent, 4 workgroups of 256 per CU (other geometries
+// measured within 2%, profiles/r01_data_ab.txt); the workgroups that carry the
+// sample history lead it (kCarryGrid, qpsk_rx_back.h)
 constexpr int kDataGrid = 1024, kDataBlock = 256;
 
 // ---------------------------------------------------------------- roles word
