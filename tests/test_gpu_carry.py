@@ -95,6 +95,20 @@ def test_history_bytes(nch, mode, shape, width, monkeypatch):
     history block equals the one built here from the inputs: the carried
     ranges hold the call's last frames and every other sample is zero."""
     _force(monkeypatch, shape, width)
+    _check_history_bytes(nch, mode)
+
+
+@modes
+def test_history_bytes_second_channel_pass(mode):
+    """The same at 4,099 channels on the default shape.  The carry runs in
+    min(256, ceil(nch / 16)) workgroups of 4 waves x 4 channels, so 4,099 is
+    the smallest count at which a wave's channel loop runs a second time; on
+    that pass 3 channels are left and the clamp min(c0 + k, nch - 1) of
+    carry_block's loads is live."""
+    _check_history_bytes(4099, mode)
+
+
+def _check_history_bytes(nch, mode):
     hi = _HEAD[mode]
     for calls in ([3], [1, 1, 1, 2]):
         x = _input(300 + nch, nch, sum(calls), 6.0)

@@ -98,8 +98,9 @@ def test_every_workgroup_shape(shape, monkeypatch):
 
 @pytest.mark.parametrize("shift", [6, 11])
 def test_low_amplitude_streams(shift):
-    """The filtered hunt's near and exact ties (see test_gpu_parity.py) under
-    the dec752 semantics."""
+    """The filtered hunt's near-ties (see test_gpu_parity.py) under the dec752
+    semantics: windows its rule leaves undecided, none with two lags at
+    exactly the maximum (those are tests/test_gpu_timing.py's impulses)."""
     x = (oracle.synth(41 + shift, 192, 12, 8.0).astype(np.int32) >> shift).astype(np.int16)
     _vs_oracle(x)
 

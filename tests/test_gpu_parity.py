@@ -123,9 +123,12 @@ def test_edge_inputs():
 @pytest.mark.parametrize("shift", [4, 8, 11])
 def test_low_amplitude_streams(shift, shape, monkeypatch):
     """Synthetic streams scaled down by 2^shift (quantised to a few int16
-    levels at 11): correlations that tie exactly or nearly, which the
-    filtered hunt hands to the exact chain (qpsk_hunt.h hunt_index); on the
-    default (dual-chain, quad) shape for this batch and forced 4x2 / 2x4d."""
+    levels at 11): correlations that nearly tie, which the filtered hunt's
+    bf16 rule leaves undecided and hands to the exact chain (qpsk_hunt.h
+    hunt_index); on the default (dual-chain, quad) shape for this batch and
+    forced 4x2 / 2x4d.  No window here has two lags at exactly the maximum
+    (replayed on the oracle's dec with tests/timing.py hunt_classes): exact
+    ties are the impulses of tests/test_gpu_timing.py."""
     if shape:
         monkeypatch.setenv("QPSK_SHAPE", shape)
     x = (oracle.synth(31 + shift, 256, 12, 8.0).astype(np.int32) >> shift).astype(np.int16)

@@ -4,47 +4,12 @@ the reference's fp32 sums S, whenever the rule commits to a lag it is the
 reference's max_index (src/qpsk.c:172-183).  The budget used here is the
 derivation's own total (2^-14.6 W), below the kernel's d = 2^-13 W; the
 rule's arithmetic (bounds, the 1 +- 2^-18 factors, the unsigned-bits max) is
-replayed in float32 as the kernel does it."""
+replayed in float32 as the kernel does it (tests/timing.py ref_sums_index and
+pick, shared with the corpora of tests/test_timing_corpus.py)."""
 import numpy as np
 
 import oracle
-
-
-def ref_sums_index(dec):
-    p = oracle.preamble().astype(np.float32)
-    dr, di = dec.real.astype(np.float32), dec.imag.astype(np.float32)
-    tr, ti = (dr - di).astype(np.float32), (di + dr).astype(np.float32)
-    n = dec.shape[0]
-    re = np.zeros((n, 128), np.float32)
-    im = np.zeros((n, 128), np.float32)
-    for i in range(128):
-        re = (re + p[i] * tr[:, i:i + 128]).astype(np.float32)
-        im = (im + p[i] * ti[:, i:i + 128]).astype(np.float32)
-    c = (re * re + im * im).astype(np.float32)
-    best = np.zeros(n, np.float32)
-    idx = np.zeros(n, np.int64)
-    for lag in range(128):
-        up = c[:, lag] > best
-        best = np.where(up, c[:, lag], best)
-        idx = np.where(up, lag, idx)
-    w = (np.abs(tr) + np.abs(ti)).sum(axis=1, dtype=np.float64).astype(np.float32)
-    return re, im, idx, w
-
-
-def pick(sr, si, w):
-    """pick_h in float32: -1 when undecided."""
-    f32 = np.float32
-    d = (w * f32(2.0 ** -13) + f32(2.0 ** -100)).astype(f32)[:, None]
-    ar, ai = np.abs(sr), np.abs(si)
-    ur, ui = (ar + d).astype(f32), (ai + d).astype(f32)
-    lr = np.maximum((ar - d).astype(f32), f32(0))
-    li = np.maximum((ai - d).astype(f32), f32(0))
-    U = ((ur * ur).astype(f32) + (ui * ui).astype(f32)).astype(f32) * f32(1 + 2.0 ** -18)
-    L = ((lr * lr).astype(f32) + (li * li).astype(f32)).astype(f32) * f32(1 - 2.0 ** -18)
-    lm = L.max(axis=1)
-    cand = U >= lm[:, None]
-    ok = (lm > 0) & (cand.sum(axis=1) == 1)
-    return np.where(ok, np.argmax(cand, axis=1), -1)
+from timing import pick, ref_sums_index
 
 
 def _windows(rng, n):
