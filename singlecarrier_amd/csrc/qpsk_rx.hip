@@ -439,47 +439,68 @@ __global__ void __launch_bounds__((64 * kWavesOf<G, FP, DUAL, W, QUAD>),
         int pf[kPf<DM>];
         if (on) prefetch<DM, false, kSplit>(srcs(a, ch0, 0), lane, pf);
         STAMP_DECL
-        for (int n = 0; n < a.F; n++) {
-            const int p = n & 1;
-            const unsigned g = a.g0 + (unsigned)n;
-            float2* wout = win_of(a, g + 1u);
-            int pmi = 0;
-            // roles bits 8-15 (stagger, kStagger): the second half of the front waves
-            // (the younger partner on each SIMD) starts each frame that many x
-            // 512 cycles late, so partners' FIR and MFMA/LDS phases interleave
-            // (MI355X_MICROARCH.md "two waves per SIMD", item 9)
-            for (int z = (f >= kFrontWaves / 2) ? roles_stagger(a.roles) : 0; z > 0; z--)
-                __builtin_amdgcn_s_sleep(8);
-            for (int c = 0; on && c < nlive; c++) {
-                const int ch = ch0 + c;
-                float2* dcur = decs[f][c % kDecBuf];
-                // the last kLateYield channels of a frame at the back wave's
-                // issue priority, so the back (the frame's last wave) gets its
-                // share before the fronts reach the barrier
-                if (c == nlive - kLateYield && roles_prio(a.roles) == kPrioFront)
-                    __builtin_amdgcn_s_setprio(0);
-                mix<DM, kSplit>(lane, pf, g, P, M);
-                STAMP(0);
-                if (c > 0) store_window(lane, pmi, decs[f][(c - 1) % kDecBuf], wout + (size_t)(ch - 1) * kWinStride);
-                {   // next channel of this frame, else the first of the next frame
-                    const bool same = c + 1 < nlive;
-                    if (same || n + 1 < a.F)
-                        prefetch<DM, false, kSplit>(srcs(a, same ? ch + 1 : ch0, same ? n : n + 1), lane, pf);
-                }
-                wave_lds_sync();
-                STAMP(1);
-                pmi = front_channel<MODE, HP, kSplit>(lane, rt_s[gi][p][cbeg + c], M, dcur, BT, p2tab,
-                                              a.heads + ((size_t)ch * a.F + n) * kHeadOut FACC_ARG);
-                if (lane == 0) mi_s[gi][p ^ 1][cbeg + c] = pmi;
-                if (c + 1 == nlive) store_window(lane, pmi, dcur, wout + (size_t)ch * kWinStride);
-                wave_lds_sync();
-                STAMP(6);
-            }
-            TAIL_ARRIVE();
-            __syncthreads();
-            if (roles_prio(a.roles) == kPrioFront) __builtin_amdgcn_s_setprio(2);
-            STAMP(7);
+        // One frame n of a 4x2 front wave's channels.  CG: frame n >= 2, so every
+        // prefetch reads consecutive rows of `in`: all 11 items from one scalar
+        // base (prefetch_rows).  The split kernel peels frames 0 and 1, which
+        // read the history, off for it (profiles/front_trim_ab.txt).
+#define QPSK_FRONT_FRAME(CG)                                                                                      \
+    do {                                                                                                          \
+        const int p = n & 1;                                                                                      \
+        const unsigned g = a.g0 + (unsigned)n;                                                                    \
+        float2* wout = win_of(a, g + 1u);                                                                         \
+        int pmi = 0;                                                                                              \
+        /* roles bits 8-15 (stagger, kStagger): the second half of the front waves */                             \
+        /* (the younger partner on each SIMD) starts each frame that many x */                                    \
+        /* 512 cycles late, so partners' FIR and MFMA/LDS phases interleave */                                    \
+        /* (MI355X_MICROARCH.md "two waves per SIMD", item 9) */                                                  \
+        for (int z = (f >= kFrontWaves / 2) ? roles_stagger(a.roles) : 0; z > 0; z--)                             \
+            __builtin_amdgcn_s_sleep(8);                                                                          \
+        for (int c = 0; on && c < nlive; c++) {                                                                   \
+            const int ch = ch0 + c;                                                                               \
+            float2* dcur = decs[f][c % kDecBuf];                                                                  \
+            /* the last kLateYield channels of a frame at the back wave's */                                      \
+            /* issue priority, so the back (the frame's last wave) gets its */                                    \
+            /* share before the fronts reach the barrier */                                                       \
+            if (c == nlive - kLateYield && roles_prio(a.roles) == kPrioFront)                                     \
+                __builtin_amdgcn_s_setprio(0);                                                                    \
+            mix<DM, kSplit>(lane, pf, g, P, M);                                                                   \
+            STAMP(0);                                                                                             \
+            if (c > 0) store_window(lane, pmi, decs[f][(c - 1) % kDecBuf], wout + (size_t)(ch - 1) * kWinStride); \
+            { /* next channel of this frame, else the first of the next frame */                                  \
+                const bool same = c + 1 < nlive;                                                                  \
+                if constexpr (CG) {                                                                               \
+                    /* scalar arithmetic only: a select on `same` would go through the VALU */                    \
+                    const int left = __builtin_amdgcn_readfirstlane(nlive - c - 1);                               \
+                    const int sm = min(left, 1); /* 1: the next channel is this frame's */                        \
+                    const int nn = n + 1 - sm;                                                                    \
+                    if (nn < a.F)                                                                                 \
+                        prefetch_rows<kSplit>(a.in + ((size_t)(ch0 + sm * (c + 1)) * a.F + (nn - 2)) * QK_FRAME,  \
+                                              lane, pf);                                                          \
+                } else if (same || n + 1 < a.F) {                                                                 \
+                    prefetch<DM, false, kSplit>(srcs(a, same ? ch + 1 : ch0, same ? n : n + 1), lane, pf);        \
+                }                                                                                                 \
+            }                                                                                                     \
+            wave_lds_sync();                                                                                      \
+            STAMP(1);                                                                                             \
+            pmi = front_channel<MODE, HP, kSplit>(lane, rt_s[gi][p][cbeg + c], M, dcur, BT, p2tab,                \
+                                          a.heads + ((size_t)ch * a.F + n) * kHeadOut FACC_ARG);                  \
+            if (lane == 0) mi_s[gi][p ^ 1][cbeg + c] = pmi;                                                       \
+            if (c + 1 == nlive) store_window(lane, pmi, dcur, wout + (size_t)ch * kWinStride);                    \
+            wave_lds_sync();                                                                                      \
+            STAMP(6);                                                                                             \
+        }                                                                                                         \
+        TAIL_ARRIVE();                                                                                            \
+        __syncthreads();                                                                                          \
+        if (roles_prio(a.roles) == kPrioFront) __builtin_amdgcn_s_setprio(2);                                     \
+        STAMP(7);                                                                                                 \
+    } while (0)
+        if constexpr (kSplit) {
+            for (int n = 0; n < a.F && n < 2; n++) QPSK_FRONT_FRAME(false);
+            for (int n = 2; n < a.F; n++) QPSK_FRONT_FRAME(true);
+        } else {
+            for (int n = 0; n < a.F; n++) QPSK_FRONT_FRAME(false);
         }
+#undef QPSK_FRONT_FRAME
         STAMP_FLUSH();
     }
 }

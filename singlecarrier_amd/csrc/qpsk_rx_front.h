@@ -38,7 +38,7 @@ __device__ __forceinline__ Src srcs(const RxArgs& a, int ch, int n) {
 
 // which frame (0: x_{n-2}, 1: x_{n-1}, 2: x_n; -1: none) and sample index of item l + 64i
 template <int MODE, int i>
-__device__ __forceinline__ int item(int lane, int& t) {
+__device__ __forceinline__ constexpr int item(int lane, int& t) {
     const int d = lane + 64 * i;
     if (i == 0) {
         if (lane < 24) { t = 1832 + 2 * lane; return 0; }
@@ -92,6 +92,46 @@ __device__ __forceinline__ int fresh_lane(int lane) {
 template <int MODE, bool CG = false, int FR = 0>
 __device__ __forceinline__ void prefetch(const Src& s, int lane, int (&r)[kPf<MODE>]) {
     prefetch_seq<MODE, CG>(s, (FR & 1) ? fresh_lane(lane) : lane, r, std::make_integer_sequence<int, kPf<MODE>>{});
+}
+
+// MODE 0, frame n >= 2 of a call, for the 4x2 split kernel: x_{n-2}, x_{n-1}
+// and x_n are consecutive rows of `in`, and there item()'s pieces meet (x_{n-2}
+// [1880 + k] is x_{n-1}[k]): item d starts 1832 + 2d samples into row x_{n-2}
+// for d < 620 and 640 samples (1280 B) further for d >= 620.  So all 11 loads
+// take one wave-uniform base, `mid` (item 5's first sample: every constant then
+// fits a load's 13-bit immediate), one lane offset, and for item 9, whose
+// lanes straddle d = 620, a second one.
+constexpr int row_item(int d) { return 1832 + 2 * d + (d < 620 ? 0 : 640); }
+template <int i>
+constexpr bool row_item_is_item() {
+    for (int l = 0; l < 64; l++) {
+        int t = 0;
+        const int f = item<0, i>(l, t);
+        if (f >= 0 && f * QK_FRAME + t != row_item(l + 64 * i)) return false;
+        if ((f >= 0) != (l + 64 * i < kItems<0>)) return false;
+    }
+    return true;
+}
+template <int... I>
+constexpr bool row_items_are_items(std::integer_sequence<int, I...>) {
+    return (row_item_is_item<I>() && ...);
+}
+static_assert(row_items_are_items(std::make_integer_sequence<int, kPf<0>>{}), "prefetch_rows: item()'s samples");
+template <int FR>
+__device__ __forceinline__ void prefetch_rows(const int16_t* xm2, int lane, int (&r)[kPf<0>]) {
+    if (FR & 1) lane = fresh_lane(lane);
+    typedef __attribute__((address_space(1))) const char gchar;   // global memory, as `in` is
+    typedef __attribute__((address_space(1))) const int gint;
+    unsigned long long m = reinterpret_cast<unsigned long long>(xm2 + row_item(64 * 5));
+    asm volatile("" : "+s"(m));   // kept as the loads' scalar base: the constants below stay immediates
+    gchar* mid = reinterpret_cast<gchar*>(m);
+    const unsigned v = 4u * (unsigned)lane;
+    const unsigned v9 = v + (lane < 620 - 64 * 9 ? 0u : 1280u);
+    auto ld = [&](unsigned voff, int imm) { return *reinterpret_cast<gint*>(mid + imm + voff); };
+#pragma unroll
+    for (int i = 0; i < 9; i++) r[i] = ld(v, 256 * (i - 5));
+    r[9] = ld(v9, 1024);
+    if (lane < kItems<0> - 640) r[10] = ld(v, 2560);
 }
 
 // src/qpsk.c:139-144 as (-1)^G * P[t] * (x * 2^-14), two samples per item.
@@ -326,14 +366,21 @@ static_assert(kSplitM1 == kM1, "qpsk_split.h: F_{n+1}'s offset in M");
 __constant__ SplitTab kSplitTab = make_split_tab();
 constexpr int kSplitTabWords = (int)sizeof(SplitTab) / 4;
 
+// Lane 63's pass-1 base and outputs differ from the other lanes' by wave-uniform
+// values only (rt, j1), so each per-lane address is one multiply-add of the
+// laundered lane, one select against an SGPR and the shift into bytes; the three
+// outputs of a lane are `st` entries apart (1, lane 63: 5), and the only one
+// discarded is D[188], lane 62's third.
 __device__ __forceinline__ void fir_split(int lane, int rt, const float2* M, float2* dec,
                                           const uint8_t* p2tab) {
     lane = fresh_lane(lane);   // the per-lane bases below are recomputed, not kept live across the loop
-    const int r = split_r(__builtin_amdgcn_readfirstlane(rt));
+    rt = __builtin_amdgcn_readfirstlane(rt);
+    const int r = split_r(rt);
     const int j1 = split_j1(r);
     const int j2 = p2tab[r * 64 + lane];
+    const bool l63 = lane == 63;
     {   // pass 1
-        const float2* b = lane < 63 ? M + 15 * lane + rt : M + kM1 + j1;
+        const float2* b = M + (l63 ? kM1 + j1 : 15 * lane + rt);
         f2 y[3] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};
 #pragma unroll
         for (int s0 = 0; s0 < 59; s0 += kFirBatch) {
@@ -354,11 +401,13 @@ __device__ __forceinline__ void fir_split(int lane, int rt, const float2* M, flo
 #pragma unroll
             for (int m = 0; m < 3; m++) anchor_f2(y[m]);
         }
+        float2* o = dec + (l63 ? QK_NDEC + j1 : 3 * lane);
+        const int st = l63 ? 5 : 1;
+        static_assert(3 * 62 + 2 == QK_NDEC, "lane 62's third output is D[188]");
 #pragma unroll
         for (int m = 0; m < 3; m++) {
-            const f2 o = y[m] * QK_GAIN;
-            const int d = lane < 63 ? 3 * lane + m : QK_NDEC + j1 + 5 * m;
-            if (d < QK_NDEC || lane == 63) dec[d] = make_float2(o.x, o.y);
+            const f2 q = y[m] * QK_GAIN;
+            if (m < 2 || lane != 62) o[m * st] = make_float2(q.x, q.y);
         }
     }
     {   // pass 2
