@@ -3,8 +3,8 @@
 Python mirror of the C-ABI in ``include/qpsk_internal.h`` (the reference's
 ``headers/qpsk_internal.h:79-84`` surface) and ``include/qpsk_batch.h`` (the
 batched, multi-channel receiver), ``include/qpsk_tx.h`` (the batched
-transmitter) and ``include/qpsk_input.h`` (G.711 and timeslot-interleaved
-input), over ``singlecarrier_amd/libqpsk_hip.so``.
+transmitter), ``include/qpsk_input.h`` (G.711 and timeslot-interleaved
+input) and ``include/qpsk_output.h`` (the same formats as output), over ``singlecarrier_amd/libqpsk_hip.so``.
 
 There is no CPU fallback: if the HIP library is missing or no GPU is present,
 the receive functions raise.  (The CPU restatement in ``oracle/`` is test
@@ -177,6 +177,16 @@ def lib():
         L.qpsk_stream_create_fmt.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int)]
         L.qpsk_stream_acquire_raw.restype = vp
         L.qpsk_stream_acquire_raw.argtypes = [vp, C.POINTER(C.c_int)]
+        L.qpsk_output_bytes.restype = C.c_size_t
+        L.qpsk_output_bytes.argtypes = [i32, i32, C.c_long, C.c_long]
+        L.qpsk_output_convert_host.argtypes = [i32, vp, C.c_long, i32, C.c_long, vp, C.c_long, i32]
+        L.qpsk_output_convert_device.argtypes = [i32, vp, C.c_long, i32, C.c_long, vp, C.c_long, vp]
+        L.qpsk_output_convert_device_w.argtypes = [i32, vp, C.c_long, i32, C.c_long, vp, C.c_long, vp,
+                                                   C.POINTER(C.c_int)]
+        L.qpsk_output_store_width.argtypes = [vp, C.c_long, i32]
+        L.qpsk_tx_batch_fmt.argtypes = [vp, vp, i32, vp, i32, C.c_long]
+        L.qpsk_tx_batch_device_fmt.argtypes = [vp, vp, i32, vp, i32, C.c_long, vp]
+        L.qpsk_tx_batch_device_fmt_path.argtypes = [vp, vp, i32, vp, i32, C.c_long, vp, i32]
         L.cnormf.restype = C.c_float
         L.cnormf.argtypes = [_CF]   # _Complex float == {float, float} in one SSE reg (SysV)
         _lib = L
@@ -200,7 +210,9 @@ SYMBOLS = ["qpsk_rx_create", "qpsk_rx_create_mode", "qpsk_rx_mode", "qpsk_rx_des
            "qpsk_tx_batch_host",
            "qpsk_input_bytes", "qpsk_input_convert_host", "qpsk_input_convert_device",
            "qpsk_rx_batch_fmt", "qpsk_rx_batch_device_fmt", "qpsk_stream_create_fmt",
-           "qpsk_stream_acquire_raw"]
+           "qpsk_stream_acquire_raw",
+           "qpsk_output_bytes", "qpsk_output_convert_host", "qpsk_output_convert_device",
+           "qpsk_tx_batch_fmt", "qpsk_tx_batch_device_fmt"]
 
 
 def _check(rc: int) -> None:
@@ -333,6 +345,86 @@ def input_convert_device(x, fmt: int, nch: int, out=None, stream=None):
         _check(lib().qpsk_input_convert_device(fmt, x.data_ptr(), ld, nch, nf, out.data_ptr(),
                                                C.c_void_p(stream.cuda_stream)))
     return out
+
+
+# output formats (include/qpsk_output.h): the same words as the input's
+OUT_S16, OUT_ALAW, OUT_ULAW = IN_S16, IN_ALAW, IN_ULAW
+OUT_PLANAR, OUT_INTERLEAVED = IN_PLANAR, IN_INTERLEAVED
+
+
+def _out_shape(fmt: int, nch: int, n: int, ld):
+    """(rows, ld) of a block's array in format `fmt`: planar [nch][ld >= n],
+    interleaved [n][ld >= nch]; ld None = the minimum."""
+    inter = (fmt & ~0x0f) == OUT_INTERLEAVED
+    least = nch if inter else n
+    ld = least if ld is None else int(ld)
+    _check(lib().qpsk_output_convert_host(fmt, None, n, nch, 0, None, ld, 1))   # the format word, nch
+    if ld < least:
+        _check(QPSK_EINVAL)
+    return (n if inter else nch), ld
+
+
+def output_bytes(fmt: int, nch: int, n: int, ld: int) -> int:
+    """qpsk_output_bytes: bytes of a block of nch channels x n samples from its
+    first element to its last (0 for arguments the conversions refuse)."""
+    return int(lib().qpsk_output_bytes(fmt, nch, n, ld))
+
+
+def output_convert_host(x, fmt: int, ld: int | None = None, out=None, threads: int = 0) -> np.ndarray:
+    """qpsk_output_convert_host: int16 [nch][n] (rows may be further apart:
+    any array with unit stride along a row) -> the block in format `fmt`, as
+    an array [nch][ld] (planar) or [n][ld] (interleaved) of int16 or uint8.
+    Only the block's elements are written: with ``out`` given, the rest of it
+    keeps its contents; otherwise the rest is zero."""
+    x = np.asarray(x)
+    if x.dtype != np.int16 or x.ndim != 2:
+        raise ValueError(f"expected int16 [nch][n], got {x.dtype} {x.shape}")
+    nch, n = x.shape
+    if n > 1 and x.strides[1] != 2 or nch > 1 and (x.strides[0] % 2 or x.strides[0] < 2 * n):
+        x = np.ascontiguousarray(x)
+    src_ld = x.strides[0] // 2 if nch > 1 else n
+    rows, ld = _out_shape(fmt, nch, n, ld)
+    if out is None:
+        out = np.zeros((rows, ld), _in_dtype(fmt))
+    elif out.dtype != _in_dtype(fmt) or out.shape != (rows, ld) or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a contiguous {np.dtype(_in_dtype(fmt)).name} [{rows}][{ld}] array")
+    threads = threads or min(16, os.cpu_count() or 1)
+    _check(lib().qpsk_output_convert_host(fmt, _ptr(x), src_ld, nch, n, _ptr(out), ld, threads))
+    return out
+
+
+def _torch_out(t, fmt: int, nch: int, n: int, what: str = "out") -> int:
+    """ld of a cuda tensor that holds a block in format `fmt`: [nch][>= n]
+    planar, [n][>= nch] interleaved, unit stride along a row, rows ld apart (a
+    column range of a wider tensor is such a block)."""
+    import torch
+    want = torch.int16 if (fmt & 0x0f) == OUT_S16 else torch.uint8
+    inter = (fmt & ~0x0f) == OUT_INTERLEAVED
+    rows, cols = (n, nch) if inter else (nch, n)
+    if not t.is_cuda or t.dtype != want or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols \
+            or (t.shape[1] > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < cols):
+        raise ValueError(f"{what} must be a cuda {want} [{rows}][>= {cols}] tensor with unit stride along a row")
+    return t.stride(0) if rows > 1 else max(t.stride(0), cols)
+
+
+def output_convert_device(x, fmt: int, out, stream=None) -> None:
+    """qpsk_output_convert_device: a cuda int16 tensor [nch][n] (unit stride
+    along a row) into ``out``, a cuda tensor that holds the block in format
+    `fmt` ([nch][>= n] planar, [n][>= nch] interleaved, possibly a column range
+    of a wider tensor); enqueued on ``stream`` (default: torch's current
+    stream).  Only the block's elements are written."""
+    import torch
+    if not x.is_cuda or x.dtype != torch.int16 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError("x must be a cuda int16 [nch][n] tensor with unit stride along a row")
+    nch, n = x.shape
+    src_ld = x.stride(0) if nch > 1 else max(x.stride(0), n)
+    _out_shape(fmt, nch, n, None)
+    ld = _torch_out(out, fmt, nch, n)
+    with torch.cuda.device(x.device):
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        _check(lib().qpsk_output_convert_device(fmt, x.data_ptr(), src_ld, nch, n, out.data_ptr(), ld,
+                                                C.c_void_p(stream.cuda_stream)))
 
 
 class Receiver:
@@ -553,6 +645,42 @@ class Transmitter:
             stream = torch.cuda.current_stream(out.device)
         _check(lib().qpsk_tx_batch_device(self._h, _ptr(bits), npk, _ptr(out), ld,
                                           C.c_void_p(stream.cuda_stream)))
+
+    def modulate_fmt(self, bits, fmt: int, ld: int | None = None, out=None) -> np.ndarray:
+        """``modulate`` with the block in format ``fmt`` (OUT_*): uint8 G.711
+        codes or int16, planar [nch][ld >= n] or interleaved [n][ld >= nch],
+        n = npackets * (1880 + gap); ld None = the minimum.  Only the block's
+        bytes cross PCIe and are written (qpsk_tx_batch_fmt): with ``out``
+        given, a contiguous array of that shape, its row tails and foreign
+        columns keep their contents; otherwise they are zero."""
+        bits = _tx_bits(bits, self.nch)
+        npk = bits.shape[1]
+        rows, ld = _out_shape(fmt, self.nch, npk * (TX_PACKET + self.gap), ld)
+        if out is None:
+            out = np.zeros((rows, ld), _in_dtype(fmt))
+        elif out.dtype != _in_dtype(fmt) or out.shape != (rows, ld) or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a contiguous {np.dtype(_in_dtype(fmt)).name} [{rows}][{ld}] array")
+        _check(lib().qpsk_tx_batch_fmt(self._h, _ptr(bits), npk, _ptr(out), fmt, ld))
+        return out
+
+    def modulate_device_fmt(self, bits, out, fmt: int, ld: int | None = None, stream=None) -> None:
+        """``modulate_device`` with the block in format ``fmt`` (OUT_*): ``out``
+        is a cuda tensor [nch][>= n] (planar) or [n][>= nch] (interleaved) of
+        uint8 codes or int16, unit stride along a row; ``ld`` defaults to its
+        row stride.  The conversion follows the modulator on ``stream``
+        (qpsk_tx_batch_device_fmt)."""
+        import torch
+        if bits.dtype != torch.uint8 or bits.dim() != 4 or bits.shape[0] != self.nch \
+                or tuple(bits.shape[2:]) != (8, NBITS) or not bits.is_contiguous() or not bits.is_cuda:
+            raise ValueError("bits must be a contiguous cuda uint8 [nch][npackets][8][62] tensor")
+        npk = bits.shape[1]
+        _out_shape(fmt, self.nch, npk * (TX_PACKET + self.gap), None)
+        row = _torch_out(out, fmt, self.nch, npk * (TX_PACKET + self.gap))
+        ld = row if ld is None else int(ld)
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device)
+        _check(lib().qpsk_tx_batch_device_fmt(self._h, _ptr(bits), npk, _ptr(out), fmt, ld,
+                                              C.c_void_p(stream.cuda_stream)))
 
 
 def tx_states(nch: int) -> np.ndarray:

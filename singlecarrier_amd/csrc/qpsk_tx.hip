@@ -34,7 +34,9 @@
 // bit per component with ballots, and kept in LDS as two bit strings.  Gap
 // positions of the tile are zeroed once and never overwritten, so the same
 // store pass writes the gap.  Row heads and tails that do not fill an aligned
-// 16 bytes are stored per int16.
+// 16 bytes are stored per int16.  The same kernel writes the planar G.711
+// formats of include/qpsk_output.h: its store pass compresses a lane's 8
+// samples into one aligned 8-byte store (heads and tails per code).
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -44,6 +46,7 @@
 
 #include "qpsk_consts.h"
 #include "qpsk_hip_host.h"
+#include "qpsk_output_fmt.h"
 #include "qpsk_tx.h"
 #include "qpsk_tx_internal.h"
 
@@ -118,11 +121,30 @@ __device__ inline void period(uint32_t wi, uint32_t wq, uint32_t live, const flo
     }
 }
 
+// 4 int16 in two dwords -> 4 G.711 codes in one
+template <int ENC>
+__device__ inline uint32_t encode4(uint32_t a, uint32_t b) {
+    auto enc = [](int x) { return ENC == QPSK_IN_ALAW ? qpsk_alaw_encode(x) : qpsk_ulaw_encode(x); };
+    return enc((int16_t)(a & 0xffffu)) | enc((int)a >> 16) << 8 | enc((int16_t)(b & 0xffffu)) << 16 |
+           enc((int)b >> 16) << 24;
+}
+
 // grid.x = 8 * channel groups (class = x & 7), grid.y = tiles of this launch
+// ENC: the element the store pass writes, int16 (QPSK_IN_S16) or the sample's
+// G.711 code (QPSK_IN_ALAW, QPSK_IN_ULAW: the planar formats of
+// include/qpsk_output.h).  A lane's 8 codes are one 8-byte store, and
+// (out + c * ld) mod 8 bytes repeats every 8 rows as (out + c * ld) mod 16
+// bytes does for int16, so the tiles, the classes and everything in front of
+// the store pass are the same.
+// (E is a parameter of its own, int16_t or uint8_t to match ENC: a signature
+// that names the format words' unnamed enum would be mangled differently by
+// the host and the device pass, and the launch would not find the kernel.)
+template <int ENC, typename E>
 __global__ void __launch_bounds__(kThreads)
 tx_batch_kernel(const uint8_t* __restrict__ bits, const uint32_t* __restrict__ state,
-                const float2* __restrict__ tab, int16_t* __restrict__ out, long ld, int nch,
-                int npk, int gap, int first, long tile0) {
+                const float2* __restrict__ tab, E* __restrict__ out, long ld, int nch, int npk, int gap,
+                int first, long tile0) {
+    static_assert(sizeof(E) == (ENC == QPSK_IN_S16 ? 2 : 1), "the element of the encoding");
     __shared__ __attribute__((aligned(16))) int16_t tile[2][kTile + 2 * kMargin];
     __shared__ uint32_t sgn[kLoop][2][kSignWords];
     const int tid = threadIdx.x;
@@ -132,8 +154,8 @@ tx_batch_kernel(const uint8_t* __restrict__ bits, const uint32_t* __restrict__ s
     const int nloop = (int)lmin((long)kLoop, (nch - cbase + kClasses - 1) / kClasses);
     const long P = (long)kTxPacket + gap;
     const long N = (long)npk * P;
-    // samples from the row's start back to a 16-byte boundary: one value per class
-    const unsigned a = (unsigned)(((uintptr_t)out >> 1) + (uint64_t)cbase * (uint64_t)ld) & (kChunk - 1);
+    // samples from the row's start back to a boundary of 8 elements: one value per class
+    const unsigned a = (unsigned)(((uintptr_t)out / sizeof(E)) + (uint64_t)cbase * (uint64_t)ld) & (kChunk - 1);
     const long pl0 = (tile0 + blockIdx.y) * kTile - (long)a;   // the tile is [pl0, pl0 + kTile)
     const long pl = pl0 > 0 ? pl0 : 0, pe = lmin(pl0 + kTile, N);
     if (pl >= pe) return;
@@ -249,13 +271,24 @@ tx_batch_kernel(const uint8_t* __restrict__ bits, const uint32_t* __restrict__ s
             else period<false>(bi, bq, 0x3ffu, ph[rd], scale[rd], buf + slot[rd]);
         }
         __syncthreads();   // one barrier per channel: the other buffer's readers passed the last one
-        int16_t* row = out + (size_t)(cbase + (long)kClasses * i) * (size_t)ld;
+        E* row = out + (size_t)(cbase + (long)kClasses * i) * (size_t)ld;
         const int16_t* src = buf + kMargin + tid * kChunk;
-        if (whole) {
-            *reinterpret_cast<uint4*>(row + p0) = *reinterpret_cast<const uint4*>(src);
+        if constexpr (ENC == QPSK_IN_S16) {
+            if (whole) {
+                *reinterpret_cast<uint4*>(row + p0) = *reinterpret_cast<const uint4*>(src);
+            } else {
+                for (int e = 0; e < kChunk; e++)
+                    if (p0 + e >= 0 && p0 + e < N) row[p0 + e] = src[e];
+            }
         } else {
-            for (int e = 0; e < kChunk; e++)
-                if (p0 + e >= 0 && p0 + e < N) row[p0 + e] = src[e];
+            if (whole) {
+                const uint4 v = *reinterpret_cast<const uint4*>(src);
+                *reinterpret_cast<uint2*>(row + p0) = make_uint2(encode4<ENC>(v.x, v.y), encode4<ENC>(v.z, v.w));
+            } else {
+                for (int e = 0; e < kChunk; e++)
+                    if (p0 + e >= 0 && p0 + e < N)
+                        row[p0 + e] = (uint8_t)(ENC == QPSK_IN_ALAW ? qpsk_alaw_encode(src[e]) : qpsk_ulaw_encode(src[e]));
+            }
         }
     }
 }
@@ -294,6 +327,9 @@ struct qpsk_tx_ctx {
     qhip::Event ev_stage[2];          // the slot's upload has been read
     int slot = 0;
     qhip::Event ev_last;              // after the latest call's kernels
+    // the modulator's int16 block of calls in another output format
+    // (qpsk_output.hip on qpsk_tx_fmt_conv); empty until such a call
+    qhip::DevBuf<int16_t> d_conv;
 };
 
 extern "C" qpsk_tx_ctx* qpsk_tx_create(int device, int nch, int gap, int* err) {
@@ -347,6 +383,28 @@ extern "C" int qpsk_tx_channels(const qpsk_tx_ctx* c) { return c ? c->nch : QPSK
 extern "C" int qpsk_tx_gap(const qpsk_tx_ctx* c) { return c ? c->gap : QPSK_EINVAL; }
 extern "C" uint64_t qpsk_tx_packets(const qpsk_tx_ctx* c) { return c ? c->packets : 0; }
 
+// the hooks of the output formats (qpsk_tx_internal.h)
+extern "C" int qpsk_tx_device(const qpsk_tx_ctx* c) { return c ? c->device : QPSK_EINVAL; }
+extern "C" void* qpsk_tx_host_stream(const qpsk_tx_ctx* c) { return c ? (hipStream_t)c->stream : nullptr; }
+
+extern "C" int qpsk_tx_fmt_conv(qpsk_tx_ctx* c, size_t n, int16_t** p) {
+    if (!c || !p) return QPSK_EINVAL;
+    HCHECK(hipSetDevice(c->device));
+    if (n > c->d_conv.cap()) {
+        HCHECK(hipDeviceSynchronize());   // an earlier call may still use the block
+        const int r = herr(c->d_conv.reserve(n));
+        if (r != QPSK_OK) return enomem(r);
+    }
+    *p = c->d_conv;
+    return QPSK_OK;
+}
+
+extern "C" int qpsk_tx_mark(qpsk_tx_ctx* c, void* stream) {
+    if (!c) return QPSK_EINVAL;
+    HCHECK(hipEventRecord(c->ev_last, (hipStream_t)stream));
+    return QPSK_OK;
+}
+
 static int tx_check(const qpsk_tx_ctx* c, const void* bits, int npackets, const void* out, long ld) {
     if (!c || npackets < 0) return QPSK_EINVAL;
     if (npackets == 0) return QPSK_OK;
@@ -356,8 +414,12 @@ static int tx_check(const qpsk_tx_ctx* c, const void* bits, int npackets, const 
     return QPSK_OK;
 }
 
-extern "C" int qpsk_tx_batch_device(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets,
-                                    int16_t* d_out, long ld, void* stream) {
+// qpsk_tx_batch_device with the element the store pass writes named: d_out is
+// int16 [nch][ld] for QPSK_IN_S16 and uint8 [nch][ld] G.711 codes for
+// QPSK_IN_ALAW / QPSK_IN_ULAW (qpsk_tx_internal.h)
+extern "C" int qpsk_tx_batch_device_enc(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets, void* d_out,
+                                        long ld, void* stream, int enc) {
+    if (enc != QPSK_IN_S16 && enc != QPSK_IN_ALAW && enc != QPSK_IN_ULAW) return QPSK_EINVAL;
     const int chk = tx_check(c, d_bits, npackets, d_out, ld);
     if (chk != QPSK_OK || npackets == 0) return chk;
     hipStream_t s = (hipStream_t)stream;
@@ -386,8 +448,17 @@ extern "C" int qpsk_tx_batch_device(qpsk_tx_ctx* c, const uint8_t* d_bits, int n
     const int first = c->packets == 0;
     for (long t0 = 0; t0 < ntile; t0 += 65535) {
         const unsigned gy = (unsigned)lmin(65535L, ntile - t0);
-        hipLaunchKernelGGL(tx_batch_kernel, dim3(gx, gy), dim3(kThreads), 0, s, d_bits, c->d_state,
-                           (const float2*)c->d_tab.get(), d_out, ld, c->nch, npackets, c->gap, first, t0);
+        const dim3 grid(gx, gy), block(kThreads);
+        const float2* tab = c->d_tab.get();
+        if (enc == QPSK_IN_S16)
+            hipLaunchKernelGGL((tx_batch_kernel<QPSK_IN_S16, int16_t>), grid, block, 0, s, d_bits, c->d_state, tab,
+                               static_cast<int16_t*>(d_out), ld, c->nch, npackets, c->gap, first, t0);
+        else if (enc == QPSK_IN_ALAW)
+            hipLaunchKernelGGL((tx_batch_kernel<QPSK_IN_ALAW, uint8_t>), grid, block, 0, s, d_bits, c->d_state, tab,
+                               static_cast<uint8_t*>(d_out), ld, c->nch, npackets, c->gap, first, t0);
+        else
+            hipLaunchKernelGGL((tx_batch_kernel<QPSK_IN_ULAW, uint8_t>), grid, block, 0, s, d_bits, c->d_state, tab,
+                               static_cast<uint8_t*>(d_out), ld, c->nch, npackets, c->gap, first, t0);
         HCHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(tx_state_kernel, dim3((unsigned)((c->nch + kThreads - 1) / kThreads)),
@@ -398,6 +469,11 @@ extern "C" int qpsk_tx_batch_device(qpsk_tx_ctx* c, const uint8_t* d_bits, int n
     c->phase[1] = ph[1];
     c->packets += (uint64_t)npackets;
     return QPSK_OK;
+}
+
+extern "C" int qpsk_tx_batch_device(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets,
+                                    int16_t* d_out, long ld, void* stream) {
+    return qpsk_tx_batch_device_enc(c, d_bits, npackets, d_out, ld, stream, QPSK_IN_S16);
 }
 
 extern "C" int qpsk_tx_batch(qpsk_tx_ctx* c, const uint8_t* bits, int npackets, int16_t* out, long ld) {
