@@ -133,6 +133,60 @@ def test_both_decoders_of_the_planar_kernel():
                 assert clean
 
 
+# ------------------------------------------------------------------ the kernels' loops
+def test_interleaved_kernel_loops_over_more_than_2_to_20_tiles():
+    """one channel x 71,400 frames = 134,232,000 samples: 1,048,688 tiles of 128
+    samples on a grid capped at 2^20 blocks, so the first 112 blocks take a
+    second tile"""
+    nch, nframes = 1, 71400
+    assert -(-nframes * sc.FRAME_SIZE // 128) == 2**20 + 112
+    rng = np.random.default_rng(20)
+    fmt = sc.IN_ALAW | sc.IN_INTERLEAVED
+    h, d = _source(rng, sc.IN_ALAW, sc.IN_INTERLEAVED, nch, 1, nframes, 0)
+    want = sc.input_convert_host(h, fmt, nch)
+    got, clean = _convert_guarded(d, fmt, nch, nframes)
+    bad = np.flatnonzero(got.reshape(-1) != want.reshape(-1))
+    assert bad.size == 0, f"{bad.size} samples differ, the first at {int(bad[0])} (tile {int(bad[0]) // 128})"
+    assert clean, "wrote outside nch * T"
+
+
+def test_planar_kernel_loops_over_more_than_2_to_28_groups():
+    """one channel x 2,284,700 frames = 4,295,236,000 codes: 2^28 + 16,794 groups
+    of 16 on a grid of 2^20 blocks x 256 lanes, so the first 66 blocks take a
+    second group, at element indices past 2^32.  Source and expectation repeat a
+    block of prime length on the device; the block's samples are the host
+    twin's.  Needs about 14 GB of device memory: skipped below 24 GiB free,
+    never shrunk (below 2^28 groups the loop does not iterate)."""
+    import torch
+    nch, nframes, L = 1, 2_284_700, 1_000_003
+    T = nframes * sc.FRAME_SIZE
+    assert (T + 15) // 16 == 2**28 + 16794
+    if torch.cuda.mem_get_info()[0] < 24 * 2**30:
+        pytest.skip("needs about 14 GB of device memory")
+    # the host twin takes whole frames: 532 frames hold the block's 1,000,003 codes
+    codes = np.random.default_rng(28).integers(0, 256, 532 * sc.FRAME_SIZE, dtype=np.uint8)
+    samples = sc.input_convert_host(codes[None], sc.IN_ULAW, 1).reshape(-1)[:L]
+    src = full = blk = exp = out = flat = None
+    try:
+        src = torch.from_numpy(codes[:L]).cuda().repeat(-(-T // L))[:T].view(1, T)
+        full = torch.full((GUARD + T + GUARD,), SENTINEL, dtype=torch.int16, device="cuda")
+        out = full[GUARD:GUARD + T].view(nch, nframes, sc.FRAME_SIZE)
+        assert out.data_ptr() % 16 == 0
+        sc.input_convert_device(src, sc.IN_ULAW, nch, out=out)
+        torch.cuda.synchronize()
+        assert bool((full[:GUARD] == SENTINEL).all()) and bool((full[GUARD + T:] == SENTINEL).all()), "wrote outside T"
+        blk = torch.from_numpy(samples).cuda()
+        flat = out.view(-1)
+        step = 2**26
+        for lo in range(0, T, step):
+            hi = min(lo + step, T)
+            exp = blk[torch.arange(lo, hi, device="cuda") % L]
+            assert torch.equal(flat[lo:hi], exp), f"samples [{lo}, {hi}) of {T} differ (groups {lo // 16}..)"
+    finally:
+        del src, full, blk, exp, out, flat
+        torch.cuda.empty_cache()
+
+
 # ------------------------------------------------------------------ the receive path
 def _encode(x, enc):
     """every sample to the code of the nearest table value"""

@@ -192,6 +192,89 @@ def test_python_converter_into_a_column_range_on_a_stream():
     np.testing.assert_array_equal(rows.cpu().numpy(), want)
 
 
+# ------------------------------------------------------------------ the kernels' loops
+@pytest.mark.parametrize("fmt", PLANAR_CODES)
+def test_planar_kernel_loops_over_more_than_65535_rows(fmt):
+    """65,537 rows of 40 samples, src_ld = 41 and ld = 43 (not flat, so rows stay
+    rows): grid.y is capped at 65,535 and rows 65,535 and 65,536 are the second
+    round of planar_kernel's row loop.  Destination 0 and 5 bytes past a 16-byte
+    boundary; with ld = 43 the rows take every offset either way."""
+    import torch
+    nch, n, sld, ld = 65537, 40, 41, 43
+    rng = np.random.default_rng(65537)
+    wide = rng.integers(-32768, 32768, (nch, sld), dtype=np.int16)
+    x = wide[:, :n]
+    d = torch.from_numpy(wide).cuda()
+    want = _host_block(x, fmt, ld)
+    arena, jobs = Arena(), []
+    for off in (0, 5):
+        jobs.append(arena.place(sc.output_bytes(fmt, nch, n, ld), off))
+    arena.alloc()
+    for pos in jobs:
+        assert _convert(fmt, d, sld, nch, n, arena.ptr(pos), ld) == 0
+        arena.expect(pos, fmt, want, ld)
+    arena.check(f"fmt {fmt:#x}: {nch} rows")
+
+
+@pytest.mark.parametrize("fmt", [sc.OUT_ALAW | sc.OUT_INTERLEAVED, sc.OUT_S16 | sc.OUT_INTERLEAVED])
+def test_interleaved_kernel_loops_over_more_than_2_to_20_tiles(fmt):
+    """one channel, 128 * 2^20 + 129 samples: 2^20 + 2 tiles of 128 samples, the
+    last of one sample, on a grid capped at 2^20 blocks, so blocks 0 and 1 take
+    a second tile.  The source repeats a block of prime length, so a tile taken
+    from the wrong place differs."""
+    import torch
+    n, L = 128 * 2**20 + 129, 1_000_003
+    assert (n + 127) // 128 == 2**20 + 2
+    block = np.random.default_rng(20).integers(-32768, 32768, L, dtype=np.int16)
+    x = np.resize(block, n)[None]
+    d = torch.from_numpy(x).cuda()
+    arena = Arena()
+    pos = arena.place(sc.output_bytes(fmt, 1, n, 1), 0)
+    arena.alloc()
+    assert _convert(fmt, d, n, 1, n, arena.ptr(pos), 1) == _es(fmt)   # ld = 1 element: the narrowest store
+    arena.expect(pos, fmt, _host_block(x, fmt, 1), 1)
+    arena.check(f"fmt {fmt:#x}: {n} samples of one channel")
+    del d, arena
+    torch.cuda.empty_cache()
+
+
+def test_planar_kernel_loops_over_more_than_2_to_28_units():
+    """one flat row of 2^32 + 4,103 samples: 2^28 + 257 units of 16 codes on a
+    grid of 2^20 blocks x 256 lanes, so the lanes of the first two blocks take a
+    second unit, at element indices past 2^32.  Source and expectation repeat a
+    block of prime length on the device; the block's codes are the host twin's.
+    The destination starts 5 bytes past a 16-byte boundary.  Needs about 17 GB
+    of device memory: skipped below 24 GiB free, never shrunk (below 2^28 units
+    the loop does not iterate)."""
+    import torch
+    fmt, n, L, off = sc.OUT_ALAW | sc.OUT_PLANAR, 2**32 + 4103, 1_000_003, 5
+    assert (off + n + 15) // 16 > 2**28
+    if torch.cuda.mem_get_info()[0] < 24 * 2**30:
+        pytest.skip("needs about 17 GB of device memory")
+    block = np.random.default_rng(28).integers(-32768, 32768, L, dtype=np.int16)
+    codes = sc.output_convert_host(block[None], fmt)[0]
+    src = full = blk = exp = out = None
+    try:
+        reps = -(-n // L)
+        src = torch.from_numpy(block).cuda().repeat(reps)[:n].view(1, n)
+        full = torch.full((GUARD + 16 + n + GUARD,), SENTINEL, dtype=torch.uint8, device="cuda")
+        start = GUARD + (off - full.data_ptr() - GUARD) % 16
+        out = full[start:start + n].view(1, n)
+        assert out.data_ptr() % 16 == off
+        sc.output_convert_device(src, fmt, out)
+        torch.cuda.synchronize()
+        assert bool((full[:start] == SENTINEL).all()) and bool((full[start + n:] == SENTINEL).all()), "wrote outside n"
+        blk = torch.from_numpy(codes).cuda()
+        step = 2**26
+        for lo in range(0, n, step):
+            hi = min(lo + step, n)
+            exp = blk[torch.arange(lo, hi, device="cuda") % L]
+            assert torch.equal(out[0, lo:hi], exp), f"codes [{lo}, {hi}) of {n} differ (units {lo // 16}..)"
+    finally:
+        del src, full, blk, exp, out
+        torch.cuda.empty_cache()
+
+
 # ------------------------------------------------------------------ the transmitter in front of it
 def _plain(tx, d_bits, N):
     """the plain call's block from the start state, as numpy [nch][N]"""

@@ -90,6 +90,29 @@ def test_against_the_oracle_and_the_reference():
     assert g[:, :, :1880].any()
 
 
+def test_a_long_stream_against_the_oracle_and_the_reference():
+    """2,049 packets on one channel (3.85 M TX samples, the carrier renormalised
+    thousands of times): the long-run pin under the GPU sweeps of
+    tests/test_gpu_tx_sweep.py, which compare with this host twin alone"""
+    npk = 2049
+    bits = np.random.default_rng(2049).integers(0, 2, (1, npk, 8, 62), dtype=np.uint8)
+    got = sc.tx_batch_host(bits, gap=0)
+    assert got.shape == (1, npk * 1880)
+    calls = packet_calls(bits[0])
+    np.testing.assert_array_equal(got[0], np.concatenate(oracle.cpu_tx(calls)))
+    if oracle.ref_available():
+        np.testing.assert_array_equal(got[0], np.concatenate(oracle.ref_tx(calls)))
+    # the gap moves samples and changes none
+    gapped = sc.tx_batch_host(bits, gap=7).reshape(npk, 1887)
+    np.testing.assert_array_equal(gapped[:, :1880].reshape(-1), got[0])
+    assert not gapped[:, 1880:].any()
+    # in 8 calls of uneven size on a carried state
+    st = sc.tx_states(1)
+    cuts = [0, 1, 2, 259, 260, 1024, 2000, 2048, 2049]
+    parts = [sc.tx_batch_host(bits[:, lo:hi], gap=0, states=st)[0] for lo, hi in zip(cuts, cuts[1:])]
+    np.testing.assert_array_equal(np.concatenate(parts), got[0])
+
+
 def test_only_a_byte_equal_to_one_is_a_one():
     """qpsk_mod's `== 1` (src/qpsk.c:252-253): 0, 2 and 255 all map to +1."""
     bits = np.random.default_rng(21).choice(np.array([0, 1, 2, 255], np.uint8), (3, 2, 8, 62))
