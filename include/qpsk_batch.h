@@ -170,9 +170,9 @@ int qpsk_rx_timing_split(qpsk_ctx *ctx, float *ms_rx, float *ms_data, int *frame
 const char *qpsk_strerror(int err);
 
 /* Provenance of the receive kernels in this library: the first 16 hex digits of
- * the sha256 of their sources and build rules (singlecarrier_amd/csrc/Makefile
- * KSRC).  Profiled counters record it; bench.py reports them only for a
- * library with the same hash. */
+ * the sha256 of their sources, their compile command and the compiler's version
+ * (singlecarrier_amd/csrc/Makefile KSRC, KCMD).  Profiled counters record it;
+ * bench.py reports them only for a library with the same hash. */
 const char *qpsk_kernel_hash(void);
 
 #ifdef __cplusplus

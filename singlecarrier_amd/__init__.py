@@ -56,16 +56,17 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
-# the receive kernels' sources and build rules, in the order the Makefile's KSRC
-# hashes them (csrc/Makefile: qpsk_kernel_hash())
+# the receive kernels' sources, in the order the Makefile's KSRC hashes them
+# (csrc/Makefile: qpsk_kernel_hash())
 KERNEL_SOURCES = ("qpsk_rx.hip", "qpsk_cmul.h", "qpsk_rx_shared.h", "qpsk_herr.h", "qpsk_rx_dev.h", "qpsk_rx_front.h",
                   "qpsk_rx_back.h", "qpsk_rx_quad.h", "qpsk_hunt.h", "qpsk_rcp.h", "qpsk_consts.h",
-                  "qpsk_fft_dev.h", "qpsk_split.h", "Makefile")
+                  "qpsk_fft_dev.h", "qpsk_split.h")
 
 
 def kernel_source_hash(csrc: str = None) -> str:
     """The hash the Makefile compiles into the library (KERNEL_SOURCES, the
-    C-ABI headers they include, the compile flags and the compiler's version),
+    C-ABI headers they include, the kernel unit's compile command and the
+    compiler's version),
     for the sources in `csrc` (default: this package's csrc/).  The Makefile is
     the one definition: this asks it (make khash)."""
     csrc = csrc or os.path.join(HERE, "csrc")

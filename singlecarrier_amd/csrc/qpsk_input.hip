@@ -27,7 +27,8 @@
 // The format entry points of the receive path and of the streams are here
 // too, on the hooks of qpsk_rx_internal.h: the receive and stream units refer
 // to nothing of this file.
-// Not part of the receive kernels' hash (csrc/Makefile KSRC).
+// Not part of the receive kernels' hash (csrc/Makefile KSRC: the kernel unit's
+// sources and compile command, not the list of objects).
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>

@@ -32,7 +32,8 @@
 // modulator into the context's int16 block and one of the kernels behind it,
 // except for planar G.711, which tx_batch_kernel's store pass writes itself
 // (the faster of the two as measured: DESIGN.md "Batched transmitter").
-// Not part of the receive kernels' hash (csrc/Makefile KSRC).
+// Not part of the receive kernels' hash (csrc/Makefile KSRC: the kernel unit's
+// sources and compile command, not the list of objects).
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>

@@ -2,7 +2,7 @@
 measurement (roofline.traffic from FETCH_SIZE/WRITE_SIZE, valu from
 SQ_INSTS_VALU) are read from committed rocprofv3 records, so they must belong
 to the library being timed.  The Makefile compiles a hash of the receive
-kernels' sources and build rules into the library (qpsk_kernel_hash());
+kernels' sources and compile command into the library (qpsk_kernel_hash());
 profiles/summarize.py stores the profiled library's hash in each record and
 bench.pmc_record() drops a record whose hash differs from the running one."""
 import json
@@ -59,11 +59,12 @@ def _mk_list(name):
 
 def test_the_hash_covers_what_the_kernel_unit_includes_and_no_host_code():
     """KSRC / KHDR are exactly the files the kernels' translation unit is made
-    from (plus the Makefile's own rules); the host side of the receive path
-    (qpsk_rx_host.*) is none of them, so a host edit keeps the counter records."""
+    from (its compile command: the tests on the hashed command below); the host
+    side of the receive path (qpsk_rx_host.*) is none of them, so a host edit
+    keeps the counter records."""
     local, api = _kernel_unit_deps()
     ksrc, khdr = _mk_list("KSRC"), _mk_list("KHDR")
-    assert len(set(ksrc)) == len(ksrc) and set(ksrc) == local | {"Makefile"}
+    assert len(set(ksrc)) == len(ksrc) and set(ksrc) == local
     assert len(set(khdr)) == len(khdr) and all(h.startswith("$(INCDIR)/") for h in khdr)
     assert {h[len("$(INCDIR)/"):] for h in khdr} == api
     host = [f for f in os.listdir(CSRC) if f.startswith("qpsk_rx_host.")]
@@ -192,3 +193,82 @@ def test_a_removed_knob_stops_the_build(knob):
     assert "error:" in r.stderr and knob.split("=")[0] in r.stderr
     ok = _syntax_only("-DQPSK_STAMPS")
     assert ok.returncode == 0, ok.stderr
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(sc.__file__)))
+
+
+def _compiles(dry):
+    """The compile commands of a dry run, as argument lists."""
+    import shlex
+    return [shlex.split(l) for l in dry.stdout.splitlines() if " -c " in l]
+
+
+@pytest.mark.parametrize("variant", [(), ("QPSK_VARIANT=-DQPSK_FIR_NOMASK=1",)])
+def test_every_flag_of_the_kernel_compile_is_hashed(variant):
+    """The compile command of build/qpsk_rx.o (dry run, the source as if just
+    edited) is the hashed command (make kcmd) token for token, once the
+    arguments that say where things lie are taken out: include directories,
+    the output, the source, the dependency file, and the hash define itself.
+    A flag written anywhere else on that command would fail this."""
+    import shlex
+    dry = _make("-n", "-W", "qpsk_rx.hip", "build/qpsk_rx.o", *variant)
+    assert dry.returncode == 0, dry.stderr
+    (cmd,) = _compiles(dry)
+    rest, it = [], iter(cmd)
+    for tok in it:
+        if tok in ("-o", "-MF"):
+            next(it)
+        elif not (tok in ("-c", "-MMD", "-MP", "qpsk_rx.hip") or tok.startswith("-I")
+                  or tok.startswith("-DQPSK_KERNEL_HASH=")):
+            rest.append(tok)
+    hashed = shlex.split(_make("kcmd", *variant).stdout)
+    assert rest == hashed
+    assert "-O3" in hashed and ("-DQPSK_FIR_NOMASK=1" in hashed) == bool(variant)
+
+
+def test_the_hash_follows_the_flags_and_not_the_makefiles_text(tmp_path):
+    cur = sc.kernel_source_hash()
+    src = tmp_path / "csrc"
+    shutil.copytree(CSRC, src, ignore=shutil.ignore_patterns("build"))
+    mk = src / "Makefile"
+    mk.write_text(mk.read_text() + "\n# one more object\nCSRC += extra.c\nREST += $(BUILD)/extra.o\n"
+                  "$(BUILD)/extra.o: extra.c\n\t$(CC) $(CFLAGS) -c -o $@ $<\n")
+    assert sc.kernel_source_hash(str(src)) == cur
+    fl = src / "flags.mk"
+    assert fl.read_text().count("-O3") == 1
+    fl.write_text(fl.read_text().replace("-O3", "-O2"))
+    assert sc.kernel_source_hash(str(src)) != cur
+
+
+def test_every_source_file_is_one_object_of_the_library():
+    objs = _make("restobj").stdout.split() + ["build/qpsk_rx.o"]
+    files = [f for f in os.listdir(CSRC) if f.endswith((".hip", ".c"))]
+    assert len(files) >= 15
+    assert sorted(objs) == sorted(f"build/{os.path.splitext(f)[0]}.o" for f in files)
+
+
+def test_the_tsan_library_compiles_every_source_of_the_product():
+    """tests/callers builds its instrumented library from the product's
+    Makefile: the same sources, none left out (dry runs, nothing is built)."""
+    import subprocess
+    tsan = subprocess.run(["make", "-n", "-B", "-C", os.path.join(ROOT, "tests", "callers"), "tsan"],
+                          capture_output=True, text=True)
+    assert tsan.returncode == 0, tsan.stderr
+    prod = _make("-n", "-B")
+    assert prod.returncode == 0, prod.stderr
+    names = [sorted(os.path.basename(c[-1]) for c in _compiles(d)) for d in (tsan, prod)]
+    assert names[0] == names[1] and len(names[1]) == len(set(names[1])) >= 15
+    assert all("-fsanitize=thread" in c for c in _compiles(tsan))
+
+
+def test_the_bit_exactness_flags_are_written_once():
+    import glob
+    files = (glob.glob(os.path.join(CSRC, "*")) + glob.glob(os.path.join(ROOT, "tests", "**", "Makefile"), recursive=True)
+             + [f for f in glob.glob(os.path.join(ROOT, "profiles", "*.sh"))
+                if not re.match(r"(r|round|call|session)\d+_", os.path.basename(f))]
+             + glob.glob(os.path.join(ROOT, "profiles", "*.py")))
+    flag = "-fno-gpu-flush-denormals-to-zero"
+    holds = [os.path.relpath(f, ROOT) for f in files
+             if os.path.isfile(f) and flag in open(f, errors="ignore").read()]
+    assert holds == [os.path.join("singlecarrier_amd", "csrc", "flags.mk")]
