@@ -42,7 +42,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PATH_PREPASS, PATH_FUSED = 0, 1   # csrc/qpsk_output_internal.h
+PATH_PREPASS, PATH_FUSED = 0, 1   # csrc/qpsk_fmt_internal.h
 
 
 def hip_runtime():

@@ -242,8 +242,29 @@ IN_S16, IN_ALAW, IN_ULAW = 0, 1, 2
 IN_PLANAR, IN_INTERLEAVED = 0, 0x10
 
 
+def _enc(fmt: int) -> int:      # IN_S16, IN_ALAW, IN_ULAW
+    return fmt & 0x0f
+
+
+def _layout(fmt: int) -> int:   # IN_PLANAR, IN_INTERLEAVED
+    return fmt & ~0x0f
+
+
 def _in_dtype(fmt: int):
-    return np.int16 if (fmt & 0x0f) == IN_S16 else np.uint8
+    return np.int16 if _enc(fmt) == IN_S16 else np.uint8
+
+
+def _threads(threads: int) -> int:
+    """Host threads of a call: the caller's, or by default up to 16."""
+    return threads or min(16, os.cpu_count() or 1)
+
+
+def _stream(stream, device):
+    """The hipStream_t of ``stream`` (default: torch's current stream on `device`)."""
+    import torch
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    return C.c_void_p(stream.cuda_stream)
 
 
 def _fmt_check(fmt: int, nch: int) -> None:
@@ -259,8 +280,7 @@ def _in_block(x, fmt: int, nch: int, what: str = "x"):
     past nch need not belong to it), T = nframes * 1880.  Works on numpy
     arrays and torch tensors alike."""
     shape = tuple(x.shape)
-    inter = (fmt & ~0x0f) == IN_INTERLEAVED
-    if inter:
+    if _layout(fmt) == IN_INTERLEAVED:
         if len(shape) != 2 or shape[1] != nch or shape[0] % FRAME_SIZE:
             raise ValueError(f"{what} must be [nframes * {FRAME_SIZE}][{nch}], got {shape}")
         return shape[0] // FRAME_SIZE, None
@@ -305,8 +325,7 @@ def input_convert_host(x, fmt: int, nch: int, threads: int = 0) -> np.ndarray:
     _fmt_check(fmt, nch)
     x, nf, ld = _np_block(x, fmt, nch)
     out = np.empty((nch, nf, FRAME_SIZE), np.int16)
-    threads = threads or min(16, os.cpu_count() or 1)
-    _check(lib().qpsk_input_convert_host(fmt, _ptr(x), ld, nch, nf, _ptr(out), threads))
+    _check(lib().qpsk_input_convert_host(fmt, _ptr(x), ld, nch, nf, _ptr(out), _threads(threads)))
     return out
 
 
@@ -314,7 +333,7 @@ def _torch_block(x, fmt: int, nch: int):
     """(nframes, ld) of a cuda tensor in format `fmt`; an interleaved block may
     be a column range of a wider tensor."""
     import torch
-    want = torch.int16 if (fmt & 0x0f) == IN_S16 else torch.uint8
+    want = torch.int16 if _enc(fmt) == IN_S16 else torch.uint8
     if not x.is_cuda or x.dtype != want:
         raise ValueError(f"format {fmt:#x} takes a cuda {want} tensor")
     nf, ld = _in_block(x, fmt, nch)
@@ -341,10 +360,8 @@ def input_convert_device(x, fmt: int, nch: int, out=None, stream=None):
             or not out.is_cuda:
         raise ValueError(f"out must be a contiguous cuda int16 [{nch}][{nf}][{FRAME_SIZE}] tensor")
     with torch.cuda.device(x.device):
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
         _check(lib().qpsk_input_convert_device(fmt, x.data_ptr(), ld, nch, nf, out.data_ptr(),
-                                               C.c_void_p(stream.cuda_stream)))
+                                               _stream(stream, x.device)))
     return out
 
 
@@ -356,13 +373,22 @@ OUT_PLANAR, OUT_INTERLEAVED = IN_PLANAR, IN_INTERLEAVED
 def _out_shape(fmt: int, nch: int, n: int, ld):
     """(rows, ld) of a block's array in format `fmt`: planar [nch][ld >= n],
     interleaved [n][ld >= nch]; ld None = the minimum."""
-    inter = (fmt & ~0x0f) == OUT_INTERLEAVED
+    inter = _layout(fmt) == OUT_INTERLEAVED
     least = nch if inter else n
     ld = least if ld is None else int(ld)
     _check(lib().qpsk_output_convert_host(fmt, None, n, nch, 0, None, ld, 1))   # the format word, nch
     if ld < least:
         _check(QPSK_EINVAL)
     return (n if inter else nch), ld
+
+
+def _out_array(out, fmt: int, rows: int, ld: int) -> np.ndarray:
+    """The [rows][ld] array a host call writes its block into: ``out``, checked, or zeros."""
+    if out is None:
+        return np.zeros((rows, ld), _in_dtype(fmt))
+    if out.dtype != _in_dtype(fmt) or out.shape != (rows, ld) or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a contiguous {np.dtype(_in_dtype(fmt)).name} [{rows}][{ld}] array")
+    return out
 
 
 def output_bytes(fmt: int, nch: int, n: int, ld: int) -> int:
@@ -385,12 +411,8 @@ def output_convert_host(x, fmt: int, ld: int | None = None, out=None, threads: i
         x = np.ascontiguousarray(x)
     src_ld = x.strides[0] // 2 if nch > 1 else n
     rows, ld = _out_shape(fmt, nch, n, ld)
-    if out is None:
-        out = np.zeros((rows, ld), _in_dtype(fmt))
-    elif out.dtype != _in_dtype(fmt) or out.shape != (rows, ld) or not out.flags.c_contiguous:
-        raise ValueError(f"out must be a contiguous {np.dtype(_in_dtype(fmt)).name} [{rows}][{ld}] array")
-    threads = threads or min(16, os.cpu_count() or 1)
-    _check(lib().qpsk_output_convert_host(fmt, _ptr(x), src_ld, nch, n, _ptr(out), ld, threads))
+    out = _out_array(out, fmt, rows, ld)
+    _check(lib().qpsk_output_convert_host(fmt, _ptr(x), src_ld, nch, n, _ptr(out), ld, _threads(threads)))
     return out
 
 
@@ -399,8 +421,8 @@ def _torch_out(t, fmt: int, nch: int, n: int, what: str = "out") -> int:
     planar, [n][>= nch] interleaved, unit stride along a row, rows ld apart (a
     column range of a wider tensor is such a block)."""
     import torch
-    want = torch.int16 if (fmt & 0x0f) == OUT_S16 else torch.uint8
-    inter = (fmt & ~0x0f) == OUT_INTERLEAVED
+    want = torch.int16 if _enc(fmt) == OUT_S16 else torch.uint8
+    inter = _layout(fmt) == OUT_INTERLEAVED
     rows, cols = (n, nch) if inter else (nch, n)
     if not t.is_cuda or t.dtype != want or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols \
             or (t.shape[1] > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < cols):
@@ -422,10 +444,29 @@ def output_convert_device(x, fmt: int, out, stream=None) -> None:
     _out_shape(fmt, nch, n, None)
     ld = _torch_out(out, fmt, nch, n)
     with torch.cuda.device(x.device):
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
         _check(lib().qpsk_output_convert_device(fmt, x.data_ptr(), src_ld, nch, n, out.data_ptr(), ld,
-                                                C.c_void_p(stream.cuda_stream)))
+                                                _stream(stream, x.device)))
+
+
+def _rx_arrays(nch: int, nf: int, trace: bool, soft: bool) -> dict:
+    """The host arrays a receive call of nf frames fills."""
+    out = {"bits": np.zeros((nch, nf, NBITS), np.uint8),
+           "valid": np.zeros((nch, nf), np.uint8)}
+    if trace:
+        out["trace"] = np.zeros((nch, nf, 4), np.int32)
+    if soft:
+        out["soft"] = np.zeros((nch, nf, DATA_SYMBOLS, 2), np.float32)
+    return out
+
+
+def _rx_tensors_check(nch: int, nf: int, bits, valid, trace, soft) -> None:
+    """The output tensors of a device receive call of nf frames."""
+    for name, t, shape in (("bits", bits, (nch, nf, NBITS)),
+                           ("valid", valid, (nch, nf)),
+                           ("trace", trace, (nch, nf, 4)),
+                           ("soft", soft, (nch, nf, DATA_SYMBOLS, 2))):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError(f"{name} must be a contiguous cuda tensor of shape {shape}")
 
 
 class Receiver:
@@ -500,12 +541,7 @@ class Receiver:
         if x.ndim != 3 or x.shape[0] != self.nch or x.shape[2] != FRAME_SIZE:
             raise ValueError(f"expected int16 [{self.nch}][nframes][{FRAME_SIZE}], got {x.shape}")
         nf = x.shape[1]
-        out = {"bits": np.zeros((self.nch, nf, NBITS), np.uint8),
-               "valid": np.zeros((self.nch, nf), np.uint8)}
-        if trace:
-            out["trace"] = np.zeros((self.nch, nf, 4), np.int32)
-        if soft:
-            out["soft"] = np.zeros((self.nch, nf, DATA_SYMBOLS, 2), np.float32)
+        out = _rx_arrays(self.nch, nf, trace, soft)
         _check(lib().qpsk_rx_batch(self._h, _ptr(x), nf, _ptr(out["bits"]), _ptr(out["valid"]),
                                    _ptr(out.get("trace")), _ptr(out.get("soft"))))
         return out
@@ -518,12 +554,7 @@ class Receiver:
         GPU (qpsk_rx_batch_fmt)."""
         _fmt_check(fmt, self.nch)
         x, nf, ld = _np_block(x, fmt, self.nch)
-        out = {"bits": np.zeros((self.nch, nf, NBITS), np.uint8),
-               "valid": np.zeros((self.nch, nf), np.uint8)}
-        if trace:
-            out["trace"] = np.zeros((self.nch, nf, 4), np.int32)
-        if soft:
-            out["soft"] = np.zeros((self.nch, nf, DATA_SYMBOLS, 2), np.float32)
+        out = _rx_arrays(self.nch, nf, trace, soft)
         _check(lib().qpsk_rx_batch_fmt(self._h, _ptr(x), fmt, ld, nf, _ptr(out["bits"]),
                                        _ptr(out["valid"]), _ptr(out.get("trace")), _ptr(out.get("soft"))))
         return out
@@ -532,19 +563,11 @@ class Receiver:
         """``demod_device`` for a cuda source block in format ``fmt`` (layouts
         as demod_fmt): conversion and receive are enqueued on ``stream``
         (qpsk_rx_batch_device_fmt)."""
-        import torch
         _fmt_check(fmt, self.nch)
         nf, ld = _torch_block(x, fmt, self.nch)
-        for name, t, shape in (("bits", bits, (self.nch, nf, NBITS)),
-                               ("valid", valid, (self.nch, nf)),
-                               ("trace", trace, (self.nch, nf, 4)),
-                               ("soft", soft, (self.nch, nf, DATA_SYMBOLS, 2))):
-            if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
-                raise ValueError(f"{name} must be a contiguous cuda tensor of shape {shape}")
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
+        _rx_tensors_check(self.nch, nf, bits, valid, trace, soft)
         _check(lib().qpsk_rx_batch_device_fmt(self._h, x.data_ptr(), fmt, ld, nf, _ptr(bits), _ptr(valid),
-                                              _ptr(trace), _ptr(soft), C.c_void_p(stream.cuda_stream)))
+                                              _ptr(trace), _ptr(soft), _stream(stream, x.device)))
 
     def sync(self) -> None:
         """Wait for the latest demod_device call; raise QpskError (QPSK_ESTALL)
@@ -559,16 +582,9 @@ class Receiver:
                 or x.shape[2] != FRAME_SIZE or not x.is_contiguous() or not x.is_cuda:
             raise ValueError("x must be a contiguous cuda int16 [nch][nframes][1880] tensor")
         nf = x.shape[1]
-        for name, t, shape in (("bits", bits, (self.nch, nf, NBITS)),
-                               ("valid", valid, (self.nch, nf)),
-                               ("trace", trace, (self.nch, nf, 4)),
-                               ("soft", soft, (self.nch, nf, DATA_SYMBOLS, 2))):
-            if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
-                raise ValueError(f"{name} must be a contiguous cuda tensor of shape {shape}")
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
+        _rx_tensors_check(self.nch, nf, bits, valid, trace, soft)
         _check(lib().qpsk_rx_batch_device(self._h, _ptr(x), nf, _ptr(bits), _ptr(valid),
-                                          _ptr(trace), _ptr(soft), C.c_void_p(stream.cuda_stream)))
+                                          _ptr(trace), _ptr(soft), _stream(stream, x.device)))
 
 
 TX_PACKET = 1880         # transmitted samples per packet: 5 * (128 + 8 * 31)
@@ -581,6 +597,15 @@ def _tx_bits(bits, nch=None):
     if bits.ndim != 4 or bits.shape[2:] != (8, NBITS) or (nch is not None and bits.shape[0] != nch):
         raise ValueError(f"expected uint8 [{nch or 'nch'}][npackets][8][{NBITS}], got {bits.shape}")
     return bits
+
+
+def _tx_bits_tensor(bits, nch: int) -> int:
+    """npackets of a device call's payload tensor."""
+    import torch
+    if bits.dtype != torch.uint8 or bits.dim() != 4 or bits.shape[0] != nch \
+            or tuple(bits.shape[2:]) != (8, NBITS) or not bits.is_contiguous() or not bits.is_cuda:
+        raise ValueError("bits must be a contiguous cuda uint8 [nch][npackets][8][62] tensor")
+    return bits.shape[1]
 
 
 class Transmitter:
@@ -632,20 +657,14 @@ class Transmitter:
         along a row and ld = out.stride(0).  Enqueues on ``stream`` (default:
         torch's current stream) and returns without synchronising."""
         import torch
-        if bits.dtype != torch.uint8 or bits.dim() != 4 or bits.shape[0] != self.nch \
-                or tuple(bits.shape[2:]) != (8, NBITS) or not bits.is_contiguous() or not bits.is_cuda:
-            raise ValueError("bits must be a contiguous cuda uint8 [nch][npackets][8][62] tensor")
-        npk = bits.shape[1]
+        npk = _tx_bits_tensor(bits, self.nch)
         if out.dtype != torch.int16 or out.dim() != 2 or out.shape[0] != self.nch or not out.is_cuda \
                 or out.shape[1] < npk * (TX_PACKET + self.gap) \
                 or (out.shape[1] > 1 and out.stride(1) != 1):
             raise ValueError("out must be a cuda int16 [nch][>= npackets * (1880 + gap)] tensor "
                              "with unit stride along a row")
         ld = out.stride(0) if self.nch > 1 else max(out.stride(0), out.shape[1])
-        if stream is None:
-            stream = torch.cuda.current_stream(out.device)
-        _check(lib().qpsk_tx_batch_device(self._h, _ptr(bits), npk, _ptr(out), ld,
-                                          C.c_void_p(stream.cuda_stream)))
+        _check(lib().qpsk_tx_batch_device(self._h, _ptr(bits), npk, _ptr(out), ld, _stream(stream, out.device)))
 
     def modulate_fmt(self, bits, fmt: int, ld: int | None = None, out=None) -> np.ndarray:
         """``modulate`` with the block in format ``fmt`` (OUT_*): uint8 G.711
@@ -657,10 +676,7 @@ class Transmitter:
         bits = _tx_bits(bits, self.nch)
         npk = bits.shape[1]
         rows, ld = _out_shape(fmt, self.nch, npk * (TX_PACKET + self.gap), ld)
-        if out is None:
-            out = np.zeros((rows, ld), _in_dtype(fmt))
-        elif out.dtype != _in_dtype(fmt) or out.shape != (rows, ld) or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a contiguous {np.dtype(_in_dtype(fmt)).name} [{rows}][{ld}] array")
+        out = _out_array(out, fmt, rows, ld)
         _check(lib().qpsk_tx_batch_fmt(self._h, _ptr(bits), npk, _ptr(out), fmt, ld))
         return out
 
@@ -670,18 +686,12 @@ class Transmitter:
         uint8 codes or int16, unit stride along a row; ``ld`` defaults to its
         row stride.  The conversion follows the modulator on ``stream``
         (qpsk_tx_batch_device_fmt)."""
-        import torch
-        if bits.dtype != torch.uint8 or bits.dim() != 4 or bits.shape[0] != self.nch \
-                or tuple(bits.shape[2:]) != (8, NBITS) or not bits.is_contiguous() or not bits.is_cuda:
-            raise ValueError("bits must be a contiguous cuda uint8 [nch][npackets][8][62] tensor")
-        npk = bits.shape[1]
+        npk = _tx_bits_tensor(bits, self.nch)
         _out_shape(fmt, self.nch, npk * (TX_PACKET + self.gap), None)
         row = _torch_out(out, fmt, self.nch, npk * (TX_PACKET + self.gap))
         ld = row if ld is None else int(ld)
-        if stream is None:
-            stream = torch.cuda.current_stream(out.device)
         _check(lib().qpsk_tx_batch_device_fmt(self._h, _ptr(bits), npk, _ptr(out), fmt, ld,
-                                              C.c_void_p(stream.cuda_stream)))
+                                              _stream(stream, out.device)))
 
 
 def tx_states(nch: int) -> np.ndarray:
@@ -707,9 +717,8 @@ def tx_batch_host(bits, gap: int = 903, states=None, threads: int = 0) -> np.nda
     if gap < 0:
         _check(QPSK_EINVAL)
     out = np.zeros((nch, npk * (TX_PACKET + gap)), np.int16)
-    threads = threads or min(16, os.cpu_count() or 1)
     _check(lib().qpsk_tx_batch_host(_ptr(states), nch, _ptr(bits), npk, gap, _ptr(out),
-                                    out.shape[1], threads))
+                                    out.shape[1], _threads(threads)))
     return out
 
 
@@ -761,7 +770,7 @@ class Stream:
         n = self.nch * self.frames * FRAME_SIZE
         buf = (C.c_uint8 * (n * np.dtype(dt).itemsize)).from_address(p)
         a = np.frombuffer(buf, dt)
-        if (self.fmt & ~0x0f) == IN_INTERLEAVED:
+        if _layout(self.fmt) == IN_INTERLEAVED:
             return a.reshape(self.frames * FRAME_SIZE, self.nch)
         return a.reshape(self.nch, self.frames * FRAME_SIZE)
 
@@ -837,9 +846,8 @@ def synth(seed: int, nch: int, nframes: int, ebn0_db: float = 1000.0, c0: int = 
           threads: int = 0) -> np.ndarray:
     """Synthetic channel streams int16 [nch][nframes][1880] (include/qpsk_synth.h)."""
     out = np.empty((nch, nframes, FRAME_SIZE), np.int16)
-    threads = threads or min(16, os.cpu_count() or 1)
     lib().qpsk_synth_batch(seed, c0, nch, float(ebn0_db), _ptr(out), nframes * FRAME_SIZE,
-                           threads)
+                           _threads(threads))
     return out
 
 

@@ -20,10 +20,11 @@
 //                       stores 128-byte runs of 8 channels.  LDS banking of both
 //                       sides: DESIGN.md (f2).
 //
-// G.711 is decoded either with the integer expansion (qpsk_input_fmt.h) or
+// G.711 is decoded either with the integer expansion (qpsk_fmt.h) or
 // through a 256-entry table in LDS that each block makes with it;
 // qpsk_input_convert_device_dec names one, profiles/input_bench.py times both,
-// and the default is the faster of each kernel (qpsk_input_internal.h).
+// and the default is the faster of each kernel (qpsk_fmt_internal.h).
+// What the kernels share with the output's is qpsk_fmt_dev.h.
 // The format entry points of the receive path and of the streams are here
 // too, on the hooks of qpsk_rx_internal.h: the receive and stream units refer
 // to nothing of this file.
@@ -34,27 +35,14 @@
 #include <stdint.h>
 
 #include "qpsk_consts.h"
+#include "qpsk_fmt_dev.h"
 #include "qpsk_herr.h"
-#include "qpsk_input.h"
-#include "qpsk_input_fmt.h"
-#include "qpsk_input_internal.h"
 #include "qpsk_rx_internal.h"
 #include "qpsk_stream.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kTC = 64;          // channels of a tile
-constexpr int kTT = 128;         // samples of a tile
-constexpr unsigned kMaxGrid = 1u << 20;
-
-template <int ENC, int DEC>
-__device__ __forceinline__ unsigned decode(unsigned code, const int16_t* tab) {
-    if constexpr (ENC == QPSK_IN_S16) return code;
-    else if constexpr (DEC == QPSK_IN_DEC_TABLE) return (unsigned)(uint16_t)tab[code];
-    else if constexpr (ENC == QPSK_IN_ALAW) return (unsigned)qpsk_alaw_decode(code) & 0xffffu;
-    else return (unsigned)qpsk_ulaw_decode(code) & 0xffffu;
-}
+using namespace qfmt;
 
 // the block's decode table (QPSK_IN_DEC_TABLE), ready after the next __syncthreads()
 template <int ENC, int DEC>
@@ -80,13 +68,6 @@ __device__ __forceinline__ void decode16(const unsigned d[4], const int16_t* tab
     o4[1] = make_uint4(p[4], p[5], p[6], p[7]);
 }
 
-// dwords Q .. Q+3 of the 8 in w, taken r bytes further on
-template <int Q>
-__device__ __forceinline__ void shifted(const unsigned w[8], unsigned r, unsigned d[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) d[j] = __builtin_amdgcn_alignbyte(w[Q + j + 1], w[Q + j], r);
-}
-
 template <int ENC, int DEC>
 __global__ __launch_bounds__(kBlock) void planar_kernel(const uint8_t* __restrict__ src,
                                                         int16_t* __restrict__ out, size_t n) {
@@ -106,32 +87,16 @@ __global__ __launch_bounds__(kBlock) void planar_kernel(const uint8_t* __restric
             const unsigned w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
             unsigned d[4];
             switch (a >> 2) {   // the same in every lane
-                case 0: shifted<0>(w, a & 3u, d); break;
-                case 1: shifted<1>(w, a & 3u, d); break;
-                case 2: shifted<2>(w, a & 3u, d); break;
-                default: shifted<3>(w, a & 3u, d); break;
+                case 0: shifted<0, 4>(w, a & 3u, d); break;
+                case 1: shifted<1, 4>(w, a & 3u, d); break;
+                case 2: shifted<2, 4>(w, a & 3u, d); break;
+                default: shifted<3, 4>(w, a & 3u, d); break;
             }
             decode16<ENC, DEC>(d, tab, out + e0);
         } else {
             for (size_t e = e0; e < e0 + 16 && e < n; e++) out[e] = (int16_t)decode<ENC, DEC>(src[e], tab);
         }
     }
-}
-
-template <int W> struct LoadOf;
-template <> struct LoadOf<1> { using type = uint8_t; };
-template <> struct LoadOf<2> { using type = uint16_t; };
-template <> struct LoadOf<4> { using type = uint32_t; };
-template <> struct LoadOf<8> { using type = uint2; };
-template <> struct LoadOf<16> { using type = uint4; };
-
-// W bytes at p (W-aligned) as dwords
-template <int W>
-__device__ __forceinline__ void load_wide(const uint8_t* p, unsigned* v) {
-    const auto x = *reinterpret_cast<const typename LoadOf<W>::type*>(p);
-    if constexpr (W == 16) v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
-    else if constexpr (W == 8) v[0] = x.x, v[1] = x.y;
-    else v[0] = x;
 }
 
 template <int ENC, int W, int DEC>
@@ -211,8 +176,6 @@ __global__ __launch_bounds__(kBlock) void interleaved_kernel(const uint8_t* __re
     }
 }
 
-unsigned grid_of(size_t blocks) { return (unsigned)(blocks < kMaxGrid ? blocks : kMaxGrid); }
-
 template <int ENC, int DEC>
 void launch_planar(const uint8_t* src, int16_t* out, size_t n, hipStream_t s) {
     const size_t groups = (n + 15) / 16;
@@ -228,39 +191,31 @@ void launch_tile(const uint8_t* src, size_t ld, unsigned nch, size_t T, int16_t*
                        out, ctiles, ntiles);
 }
 
-template <int ENC, int DEC>
-void launch_interleaved(int w, const uint8_t* src, size_t ld, unsigned nch, size_t T, int16_t* out, hipStream_t s) {
-    switch (w) {
-        case 16: return launch_tile<ENC, 16, DEC>(src, ld, nch, T, out, s);
-        case 8: return launch_tile<ENC, 8, DEC>(src, ld, nch, T, out, s);
-        case 4: return launch_tile<ENC, 4, DEC>(src, ld, nch, T, out, s);
-        case 2: return launch_tile<ENC, 2, DEC>(src, ld, nch, T, out, s);
-        default:
-            if constexpr (ENC != QPSK_IN_S16) launch_tile<ENC, 1, DEC>(src, ld, nch, T, out, s);
-            return;
-    }
+// f(Const<enc>, Const<dec>): int16 has no decoder, so only its QPSK_IN_DEC_ARITH kernels exist
+template <class F>
+void with_decoder(int enc, bool table, F&& f) {
+    with_encoding(enc, [&](auto e) {
+        if constexpr (e() != QPSK_IN_S16) {
+            if (table) return f(e, Const<QPSK_IN_DEC_TABLE>{});
+        }
+        f(e, Const<QPSK_IN_DEC_ARITH>{});
+    });
 }
 
 }  // namespace
 
-// The widest load every row of an interleaved block allows: a tile's rows start
-// at src + (t * ld + 64 * i) * esize, so the address of the block and the byte
-// stride of its rows decide for the whole call.
 extern "C" int qpsk_input_load_width(const void* d_src, long ld, int esize) {
-    const uintptr_t m = reinterpret_cast<uintptr_t>(d_src) | (uintptr_t)ld * (uintptr_t)esize;
-    int w = 16;
-    while (w > esize && (m & (uintptr_t)(w - 1)) != 0) w >>= 1;
-    return w;
+    return fmt_access_width(d_src, ld, esize);
 }
 
 extern "C" int qpsk_input_convert_device_dec(int fmt, const void* d_src, long ld, int nch, int nframes,
                                              int16_t* d_out, void* stream, int dec) {
     if (qpsk_input_check(fmt, nch, nframes, ld) != QPSK_OK) return QPSK_EINVAL;
     if (dec == QPSK_IN_DEC_DEFAULT)
-        dec = QPSK_IN_LAYOUT(fmt) == QPSK_IN_PLANAR ? QPSK_IN_DEC_TABLE : QPSK_IN_DEC_ARITH;
+        dec = QPSK_FMT_LAYOUT(fmt) == QPSK_IN_PLANAR ? QPSK_IN_DEC_TABLE : QPSK_IN_DEC_ARITH;
     if (dec != QPSK_IN_DEC_ARITH && dec != QPSK_IN_DEC_TABLE) return QPSK_EINVAL;
     if (nframes == 0) return QPSK_OK;
-    const int es = qpsk_input_esize(fmt), enc = QPSK_IN_ENC(fmt);
+    const int es = qpsk_fmt_esize(fmt), enc = QPSK_FMT_ENC(fmt);
     if (!d_src || !d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u) != 0 ||
         (reinterpret_cast<uintptr_t>(d_src) & (uintptr_t)(es - 1)) != 0)
         return QPSK_EINVAL;
@@ -268,30 +223,21 @@ extern "C" int qpsk_input_convert_device_dec(int fmt, const void* d_src, long ld
     const uint8_t* src = static_cast<const uint8_t*>(d_src);
     const size_t T = (size_t)nframes * QK_FRAME, n = (size_t)nch * T;
     const bool table = dec == QPSK_IN_DEC_TABLE;
-    if (QPSK_IN_LAYOUT(fmt) == QPSK_IN_PLANAR) {
+    if (QPSK_FMT_LAYOUT(fmt) == QPSK_IN_PLANAR) {
         if (enc == QPSK_IN_S16) {
             HCHECK(hipMemcpyAsync(d_out, d_src, n * sizeof(int16_t), hipMemcpyDeviceToDevice, s));
             return QPSK_OK;
         }
-        if (enc == QPSK_IN_ALAW) {
-            if (table) launch_planar<QPSK_IN_ALAW, QPSK_IN_DEC_TABLE>(src, d_out, n, s);
-            else launch_planar<QPSK_IN_ALAW, QPSK_IN_DEC_ARITH>(src, d_out, n, s);
-        } else {
-            if (table) launch_planar<QPSK_IN_ULAW, QPSK_IN_DEC_TABLE>(src, d_out, n, s);
-            else launch_planar<QPSK_IN_ULAW, QPSK_IN_DEC_ARITH>(src, d_out, n, s);
-        }
+        with_decoder(enc, table, [&](auto e, auto d) {
+            if constexpr (e() != QPSK_IN_S16) launch_planar<e(), d()>(src, d_out, n, s);
+        });
     } else {
         const int w = qpsk_input_load_width(d_src, ld, es);
-        const unsigned uc = (unsigned)nch;
-        if (enc == QPSK_IN_S16) {
-            launch_interleaved<QPSK_IN_S16, QPSK_IN_DEC_ARITH>(w, src, (size_t)ld, uc, T, d_out, s);
-        } else if (enc == QPSK_IN_ALAW) {
-            if (table) launch_interleaved<QPSK_IN_ALAW, QPSK_IN_DEC_TABLE>(w, src, (size_t)ld, uc, T, d_out, s);
-            else launch_interleaved<QPSK_IN_ALAW, QPSK_IN_DEC_ARITH>(w, src, (size_t)ld, uc, T, d_out, s);
-        } else {
-            if (table) launch_interleaved<QPSK_IN_ULAW, QPSK_IN_DEC_TABLE>(w, src, (size_t)ld, uc, T, d_out, s);
-            else launch_interleaved<QPSK_IN_ULAW, QPSK_IN_DEC_ARITH>(w, src, (size_t)ld, uc, T, d_out, s);
-        }
+        with_decoder(enc, table, [&](auto e, auto d) {
+            with_width<esize_of(e())>(w, [&](auto wc) {
+                launch_tile<e(), wc(), d()>(src, (size_t)ld, (unsigned)nch, T, d_out, s);
+            });
+        });
     }
     HCHECK(hipGetLastError());
     return QPSK_OK;

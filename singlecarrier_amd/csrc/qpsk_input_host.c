@@ -1,18 +1,18 @@
 /*
  * qpsk_input_host.c -- qpsk_input_bytes and qpsk_input_convert_host
  * (include/qpsk_input.h): the input conversion's contract on the host.  G.711
- * codes through a 256-entry table made from the expansion in qpsk_input_fmt.h;
+ * codes through a 256-entry table made from the expansion in qpsk_fmt.h;
  * threads over channels (qpsk_fanout), like qpsk_tx_host.c.  One
  * self-contained source: the sanitizer build of tests/callers takes it alone.
  */
 #include <string.h>
 
 #include "qpsk_fanout.h"
-#include "qpsk_input_fmt.h"
+#include "qpsk_fmt.h"
 
 size_t qpsk_input_bytes(int fmt, int nch, int nframes, long ld) {
     if (qpsk_input_check(fmt, nch, nframes, ld) != QPSK_OK || nframes == 0) return 0;
-    return qpsk_input_elems(fmt, nch, nframes, ld) * (size_t)qpsk_input_esize(fmt);
+    return qpsk_input_elems(fmt, nch, nframes, ld) * (size_t)qpsk_fmt_esize(fmt);
 }
 
 typedef struct {
@@ -53,8 +53,8 @@ int qpsk_input_convert_host(int fmt, const void *src, long ld, int nch, int nfra
     job.src = (const uint8_t *)src;
     job.out = out;
     job.T = (size_t)nframes * QK_FRAME;
-    job.enc = QPSK_IN_ENC(fmt);
-    if (QPSK_IN_LAYOUT(fmt) == QPSK_IN_INTERLEAVED) {
+    job.enc = QPSK_FMT_ENC(fmt);
+    if (QPSK_FMT_LAYOUT(fmt) == QPSK_IN_INTERLEAVED) {
         job.cstride = 1;
         job.tstride = (size_t)ld;
     } else {

@@ -26,7 +26,8 @@
 //
 // Every store is inside the block: no wider word that reaches outside it is
 // read, modified and written back.
-// G.711 is the integer compression of qpsk_output_fmt.h.
+// G.711 is the integer compression of qpsk_fmt.h; what the kernels share with
+// the input's is qpsk_fmt_dev.h.
 // The format entry points of the transmitter are here too, on the hooks of
 // qpsk_tx_internal.h: qpsk_tx.hip refers to nothing of this file.  They run the
 // modulator into the context's int16 block and one of the kernels behind it,
@@ -39,44 +40,16 @@
 #include <stdint.h>
 
 #include "qpsk_consts.h"
+#include "qpsk_fmt_dev.h"
 #include "qpsk_herr.h"
 #include "qpsk_hip_host.h"
-#include "qpsk_output.h"
-#include "qpsk_output_fmt.h"
-#include "qpsk_output_internal.h"
 #include "qpsk_tx_internal.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kTC = 64;          // channels of a tile
-constexpr int kTT = 128;         // samples of a tile
+using namespace qfmt;
+
 constexpr int kChunk = 8;        // samples of a lane's global load in the tile kernel
-constexpr unsigned kMaxGrid = 1u << 20;
-
-template <int ENC>
-__device__ __forceinline__ unsigned encode(int x) {
-    if constexpr (ENC == QPSK_IN_S16) return (unsigned)x & 0xffffu;
-    else if constexpr (ENC == QPSK_IN_ALAW) return qpsk_alaw_encode(x);
-    else return qpsk_ulaw_encode(x);
-}
-
-__device__ __forceinline__ int lo16(unsigned d) { return (int)(int16_t)(d & 0xffffu); }
-__device__ __forceinline__ int hi16(unsigned d) { return (int)d >> 16; }
-
-// 4 int16 in two dwords -> 4 codes in one
-template <int ENC>
-__device__ __forceinline__ unsigned encode4(unsigned a, unsigned b) {
-    return encode<ENC>(lo16(a)) | encode<ENC>(hi16(a)) << 8 | encode<ENC>(lo16(b)) << 16 |
-           encode<ENC>(hi16(b)) << 24;
-}
-
-// dwords Q .. Q+7 of the 12 in w, taken r bytes further on
-template <int Q>
-__device__ __forceinline__ void shifted(const unsigned w[12], unsigned r, unsigned d[8]) {
-#pragma unroll
-    for (int j = 0; j < 8; j++) d[j] = __builtin_amdgcn_alignbyte(w[Q + j + 1], w[Q + j], r);
-}
 
 // grid.y strides over rows, grid.x * kBlock over a row's aligned 16-byte units
 template <int ENC>
@@ -103,10 +76,10 @@ __global__ __launch_bounds__(kBlock) void planar_kernel(const int16_t* __restric
                 const unsigned w[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, x.x, x.y, x.z, x.w};
                 unsigned d[8];
                 switch (r >> 2) {   // the same in every lane of the block
-                    case 0: shifted<0>(w, r & 3u, d); break;
-                    case 1: shifted<1>(w, r & 3u, d); break;
-                    case 2: shifted<2>(w, r & 3u, d); break;
-                    default: shifted<3>(w, r & 3u, d); break;
+                    case 0: shifted<0, 8>(w, r & 3u, d); break;
+                    case 1: shifted<1, 8>(w, r & 3u, d); break;
+                    case 2: shifted<2, 8>(w, r & 3u, d); break;
+                    default: shifted<3, 8>(w, r & 3u, d); break;
                 }
                 *reinterpret_cast<uint4*>(drow + e0) =
                     make_uint4(encode4<ENC>(d[0], d[1]), encode4<ENC>(d[2], d[3]), encode4<ENC>(d[4], d[5]),
@@ -118,22 +91,6 @@ __global__ __launch_bounds__(kBlock) void planar_kernel(const int16_t* __restric
             }
         }
     }
-}
-
-template <int W> struct StoreOf;
-template <> struct StoreOf<1> { using type = uint8_t; };
-template <> struct StoreOf<2> { using type = uint16_t; };
-template <> struct StoreOf<4> { using type = uint32_t; };
-template <> struct StoreOf<8> { using type = uint2; };
-template <> struct StoreOf<16> { using type = uint4; };
-
-// W bytes in dwords to p (W-aligned)
-template <int W>
-__device__ __forceinline__ void store_wide(uint8_t* p, const unsigned* v) {
-    using T = typename StoreOf<W>::type;
-    if constexpr (W == 16) *reinterpret_cast<T*>(p) = make_uint4(v[0], v[1], v[2], v[3]);
-    else if constexpr (W == 8) *reinterpret_cast<T*>(p) = make_uint2(v[0], v[1]);
-    else *reinterpret_cast<T*>(p) = (T)v[0];
 }
 
 // The tile in LDS: element (c, p) at c * RS + skew(c) + p * ES.  Rows along time
@@ -149,7 +106,7 @@ template <int ENC, int W>
 __global__ __launch_bounds__(kBlock) void interleaved_kernel(const int16_t* __restrict__ src, size_t src_ld,
                                                              unsigned nch, size_t n, uint8_t* __restrict__ dst,
                                                              size_t ld, unsigned ctiles, size_t ntiles) {
-    constexpr int ES = ENC == QPSK_IN_S16 ? 2 : 1;   // bytes of an element
+    constexpr int ES = ENC == QPSK_OUT_S16 ? 2 : 1;   // bytes of an element
     constexpr int RS = kTT * ES + 4;                 // bytes of a tile row in LDS
     constexpr int V = W / ES;                        // elements of a lane's store
     constexpr int LPR = kTC / V;                     // lanes that store a destination row of the tile
@@ -232,13 +189,11 @@ __global__ __launch_bounds__(kBlock) void interleaved_kernel(const int16_t* __re
     }
 }
 
-unsigned grid_of(size_t blocks, unsigned cap) { return (unsigned)(blocks < cap ? (blocks ? blocks : 1) : cap); }
-
 template <int ENC>
 void launch_planar(const int16_t* src, size_t src_ld, uint8_t* dst, size_t ld, unsigned nch, size_t n,
                    hipStream_t s) {
     const size_t units = (n + 30) / 16;   // of the row with the longest head
-    hipLaunchKernelGGL((planar_kernel<ENC>), dim3(grid_of((units + kBlock - 1) / kBlock, kMaxGrid), grid_of(nch, 65535u)),
+    hipLaunchKernelGGL((planar_kernel<ENC>), dim3(grid_of((units + kBlock - 1) / kBlock), grid_of(nch, 65535u)),
                        dim3(kBlock), 0, s, src, src_ld, dst, ld, nch, n);
 }
 
@@ -247,35 +202,14 @@ void launch_tile(const int16_t* src, size_t src_ld, unsigned nch, size_t n, uint
                  hipStream_t s) {
     const unsigned ctiles = (nch + kTC - 1) / kTC;
     const size_t ntiles = (size_t)ctiles * ((n + kTT - 1) / kTT);
-    hipLaunchKernelGGL((interleaved_kernel<ENC, W>), dim3(grid_of(ntiles, kMaxGrid)), dim3(kBlock), 0, s, src, src_ld,
+    hipLaunchKernelGGL((interleaved_kernel<ENC, W>), dim3(grid_of(ntiles)), dim3(kBlock), 0, s, src, src_ld,
                        nch, n, dst, ld, ctiles, ntiles);
-}
-
-template <int ENC>
-void launch_interleaved(int w, const int16_t* src, size_t src_ld, unsigned nch, size_t n, uint8_t* dst, size_t ld,
-                        hipStream_t s) {
-    switch (w) {
-        case 16: return launch_tile<ENC, 16>(src, src_ld, nch, n, dst, ld, s);
-        case 8: return launch_tile<ENC, 8>(src, src_ld, nch, n, dst, ld, s);
-        case 4: return launch_tile<ENC, 4>(src, src_ld, nch, n, dst, ld, s);
-        case 2: return launch_tile<ENC, 2>(src, src_ld, nch, n, dst, ld, s);
-        default:
-            if constexpr (ENC != QPSK_IN_S16) launch_tile<ENC, 1>(src, src_ld, nch, n, dst, ld, s);
-            return;
-    }
 }
 
 }  // namespace
 
-// The widest store every row of an interleaved block allows: a tile's rows
-// start at dst + (p * ld + 64 * i) * esize, so the address of the block and the
-// byte stride of its rows decide for the whole call; the run's last channels,
-// where nch is no multiple of the lane's elements, go per element.
 extern "C" int qpsk_output_store_width(const void* d_dst, long ld, int esize) {
-    const uintptr_t m = reinterpret_cast<uintptr_t>(d_dst) | (uintptr_t)ld * (uintptr_t)esize;
-    int w = 16;
-    while (w > esize && (m & (uintptr_t)(w - 1)) != 0) w >>= 1;
-    return w;
+    return fmt_access_width(d_dst, ld, esize);
 }
 
 extern "C" int qpsk_output_convert_device_w(int fmt, const int16_t* d_src, long src_ld, int nch, long n,
@@ -283,15 +217,15 @@ extern "C" int qpsk_output_convert_device_w(int fmt, const int16_t* d_src, long 
     if (width) *width = 0;
     if (qpsk_output_check(fmt, nch, n, src_ld, ld) != QPSK_OK) return QPSK_EINVAL;
     if (n == 0) return QPSK_OK;
-    const int es = qpsk_input_esize(fmt), enc = QPSK_IN_ENC(fmt);
+    const int es = qpsk_fmt_esize(fmt), enc = QPSK_FMT_ENC(fmt);
     if (!d_src || !d_dst || (reinterpret_cast<uintptr_t>(d_src) & 1u) != 0 ||
         (reinterpret_cast<uintptr_t>(d_dst) & (uintptr_t)(es - 1)) != 0)
         return QPSK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     uint8_t* dst = static_cast<uint8_t*>(d_dst);
     const unsigned uc = (unsigned)nch;
-    if (QPSK_IN_LAYOUT(fmt) == QPSK_IN_PLANAR) {
-        if (enc == QPSK_IN_S16) {   // rows of n samples, ld apart
+    if (QPSK_FMT_LAYOUT(fmt) == QPSK_OUT_PLANAR) {
+        if (enc == QPSK_OUT_S16) {   // rows of n samples, ld apart
             HCHECK(hipMemcpy2DAsync(d_dst, sizeof(int16_t) * (size_t)ld, d_src, sizeof(int16_t) * (size_t)src_ld,
                                     sizeof(int16_t) * (size_t)n, (size_t)nch, hipMemcpyDeviceToDevice, s));
             return QPSK_OK;
@@ -300,14 +234,17 @@ extern "C" int qpsk_output_convert_device_w(int fmt, const int16_t* d_src, long 
         const bool flat = src_ld == n && ld == n;
         const unsigned rows = flat ? 1u : uc;
         const size_t len = flat ? (size_t)nch * (size_t)n : (size_t)n;
-        if (enc == QPSK_IN_ALAW) launch_planar<QPSK_IN_ALAW>(d_src, (size_t)src_ld, dst, (size_t)ld, rows, len, s);
-        else launch_planar<QPSK_IN_ULAW>(d_src, (size_t)src_ld, dst, (size_t)ld, rows, len, s);
+        with_encoding(enc, [&](auto e) {
+            if constexpr (e() != QPSK_OUT_S16) launch_planar<e()>(d_src, (size_t)src_ld, dst, (size_t)ld, rows, len, s);
+        });
     } else {
         const int w = qpsk_output_store_width(d_dst, ld, es);
         if (width) *width = w;
-        if (enc == QPSK_IN_S16) launch_interleaved<QPSK_IN_S16>(w, d_src, (size_t)src_ld, uc, (size_t)n, dst, (size_t)ld, s);
-        else if (enc == QPSK_IN_ALAW) launch_interleaved<QPSK_IN_ALAW>(w, d_src, (size_t)src_ld, uc, (size_t)n, dst, (size_t)ld, s);
-        else launch_interleaved<QPSK_IN_ULAW>(w, d_src, (size_t)src_ld, uc, (size_t)n, dst, (size_t)ld, s);
+        with_encoding(enc, [&](auto e) {
+            with_width<esize_of(e())>(w, [&](auto wc) {
+                launch_tile<e(), wc()>(d_src, (size_t)src_ld, uc, (size_t)n, dst, (size_t)ld, s);
+            });
+        });
     }
     HCHECK(hipGetLastError());
     return QPSK_OK;
@@ -321,16 +258,13 @@ extern "C" int qpsk_output_convert_device(int fmt, const int16_t* d_src, long sr
 // ---------------------------------------------------------------- the transmitter in front of it
 namespace {
 
-constexpr long kTxPacket = 1880;
-constexpr size_t kPacketBits = 496;
-
 // what qpsk_tx_batch refuses, and the block's own checks; *N = samples of a row
 int tx_fmt_check(const qpsk_tx_ctx* c, const void* bits, int npackets, const void* out, int fmt, long ld, long* N) {
     const int nch = qpsk_tx_channels(c), gap = qpsk_tx_gap(c);   // QPSK_EINVAL for a null context
-    if (nch < 1 || gap < 0 || npackets < 0 || qpsk_input_esize(fmt) == 0) return QPSK_EINVAL;
-    *N = (long)npackets * (kTxPacket + gap);
+    if (nch < 1 || gap < 0 || npackets < 0 || qpsk_fmt_esize(fmt) == 0) return QPSK_EINVAL;
+    *N = (long)npackets * ((long)QPSK_TX_PACKET + gap);
     if (npackets == 0) return QPSK_OK;
-    if (!bits || !out || (long)nch * npackets >= (1L << 28)) return QPSK_EINVAL;
+    if (!bits || !out || (long)nch * npackets >= QPSK_TX_MAX_CHANNEL_PACKETS) return QPSK_EINVAL;
     return qpsk_output_check(fmt, nch, *N, *N, ld);
 }
 
@@ -345,13 +279,13 @@ extern "C" int qpsk_tx_batch_device_fmt_path(qpsk_tx_ctx* c, const uint8_t* d_bi
         return qpsk_tx_batch_device(c, d_bits, npackets, static_cast<int16_t*>(d_out), ld, stream);
     long N = 0;
     const int chk = tx_fmt_check(c, d_bits, npackets, d_out, fmt, ld, &N);
-    const bool fusable = QPSK_IN_LAYOUT(fmt) == QPSK_IN_PLANAR && QPSK_IN_ENC(fmt) != QPSK_IN_S16;
+    const bool fusable = QPSK_FMT_LAYOUT(fmt) == QPSK_OUT_PLANAR && QPSK_FMT_ENC(fmt) != QPSK_OUT_S16;
     if (path == QPSK_OUT_PATH_DEFAULT) path = fusable ? QPSK_OUT_PATH_FUSED : QPSK_OUT_PATH_PREPASS;
     if ((path != QPSK_OUT_PATH_PREPASS && path != QPSK_OUT_PATH_FUSED) || (path == QPSK_OUT_PATH_FUSED && !fusable))
         return QPSK_EINVAL;
     if (chk != QPSK_OK || npackets == 0) return chk;
     if (path == QPSK_OUT_PATH_FUSED)   // the modulator's store pass writes the codes
-        return qpsk_tx_batch_device_enc(c, d_bits, npackets, d_out, ld, stream, QPSK_IN_ENC(fmt));
+        return qpsk_tx_batch_device_enc(c, d_bits, npackets, d_out, ld, stream, QPSK_FMT_ENC(fmt));
     const int nch = qpsk_tx_channels(c);
     const long sld = conv_ld(N);
     int16_t* conv = nullptr;
@@ -378,11 +312,11 @@ extern "C" int qpsk_tx_batch_fmt(qpsk_tx_ctx* c, const uint8_t* bits, int npacke
     HCHECK(hipSetDevice(qpsk_tx_device(c)));
     hipStream_t s = (hipStream_t)qpsk_tx_host_stream(c);
     const int nch = qpsk_tx_channels(c);
-    const size_t es = (size_t)qpsk_input_esize(fmt);
-    const bool inter = QPSK_IN_LAYOUT(fmt) == QPSK_IN_INTERLEAVED;
+    const size_t es = (size_t)qpsk_fmt_esize(fmt);
+    const bool inter = QPSK_FMT_LAYOUT(fmt) == QPSK_OUT_INTERLEAVED;
     // the block on the device is dense: rows of `width` bytes, `rows` of them
     const size_t width = (inter ? (size_t)nch : (size_t)N) * es, rows = inter ? (size_t)N : (size_t)nch;
-    const size_t nbits = (size_t)nch * (size_t)npackets * kPacketBits;
+    const size_t nbits = (size_t)nch * (size_t)npackets * QPSK_TX_PACKET_BITS;
     qhip::DevBuf<uint8_t> d_bits, d_block;   // released on return, after the synchronisation
     int r = herr(d_bits.reserve(nbits));
     if (r == QPSK_OK) r = herr(d_block.reserve(width * rows));

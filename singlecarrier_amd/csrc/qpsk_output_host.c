@@ -1,18 +1,18 @@
 /*
  * qpsk_output_host.c -- qpsk_output_bytes and qpsk_output_convert_host
  * (include/qpsk_output.h): the output conversion's contract on the host.  G.711
- * codes by the integer compression of qpsk_output_fmt.h; threads over channels
+ * codes by the integer compression of qpsk_fmt.h; threads over channels
  * (qpsk_fanout), like qpsk_input_host.c.  One self-contained source: the
  * sanitizer build of the tests takes it alone.
  */
 #include <string.h>
 
 #include "qpsk_fanout.h"
-#include "qpsk_output_fmt.h"
+#include "qpsk_fmt.h"
 
 size_t qpsk_output_bytes(int fmt, int nch, long n, long ld) {
     if (qpsk_output_check(fmt, nch, n, n, ld) != QPSK_OK || n == 0) return 0;
-    return qpsk_output_elems(fmt, nch, n, ld) * (size_t)qpsk_input_esize(fmt);
+    return qpsk_output_elems(fmt, nch, n, ld) * (size_t)qpsk_fmt_esize(fmt);
 }
 
 typedef struct {
@@ -33,9 +33,9 @@ static void share(void *arg, int lo, int hi) {
         for (int c = lo; c < hi; c++) {
             const int16_t *s = j->src + (size_t)c * j->src_ld;
             const size_t base = (size_t)c * j->cstride;
-            if (j->enc == QPSK_IN_S16) {
+            if (j->enc == QPSK_OUT_S16) {
                 for (size_t p = p0; p < p1; p++) memcpy(j->dst + 2 * (base + p * j->tstride), &s[p], 2);
-            } else if (j->enc == QPSK_IN_ALAW) {
+            } else if (j->enc == QPSK_OUT_ALAW) {
                 for (size_t p = p0; p < p1; p++) j->dst[base + p * j->tstride] = (uint8_t)qpsk_alaw_encode(s[p]);
             } else {
                 for (size_t p = p0; p < p1; p++) j->dst[base + p * j->tstride] = (uint8_t)qpsk_ulaw_encode(s[p]);
@@ -54,8 +54,8 @@ int qpsk_output_convert_host(int fmt, const int16_t *src, long src_ld, int nch, 
     job.dst = (uint8_t *)dst;
     job.n = (size_t)n;
     job.src_ld = (size_t)src_ld;
-    job.enc = QPSK_IN_ENC(fmt);
-    if (QPSK_IN_LAYOUT(fmt) == QPSK_IN_INTERLEAVED) {
+    job.enc = QPSK_FMT_ENC(fmt);
+    if (QPSK_FMT_LAYOUT(fmt) == QPSK_OUT_INTERLEAVED) {
         job.cstride = 1;
         job.tstride = (size_t)ld;
     } else {

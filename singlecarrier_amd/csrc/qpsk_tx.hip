@@ -45,8 +45,8 @@
 #include <string.h>
 
 #include "qpsk_consts.h"
+#include "qpsk_fmt_dev.h"
 #include "qpsk_hip_host.h"
-#include "qpsk_output_fmt.h"
 #include "qpsk_tx.h"
 #include "qpsk_tx_internal.h"
 
@@ -54,9 +54,9 @@
 
 namespace {
 
-constexpr int kTxPacket = 1880;    // transmitted samples per packet
+constexpr int kTxPacket = QPSK_TX_PACKET;         // qpsk_tx_internal.h
+constexpr int kPacketBits = QPSK_TX_PACKET_BITS;
 constexpr int kSymPacket = 376;    // 128 + 8*31 symbols per packet
-constexpr int kPacketBits = 496;   // payload bytes per packet
 constexpr int kHist = 9;           // earlier symbols a sample's FIR window reaches
 constexpr int kThreads = 256;
 constexpr int kChunk = 8;                    // samples per 16-byte store
@@ -121,17 +121,9 @@ __device__ inline void period(uint32_t wi, uint32_t wq, uint32_t live, const flo
     }
 }
 
-// 4 int16 in two dwords -> 4 G.711 codes in one
-template <int ENC>
-__device__ inline uint32_t encode4(uint32_t a, uint32_t b) {
-    auto enc = [](int x) { return ENC == QPSK_IN_ALAW ? qpsk_alaw_encode(x) : qpsk_ulaw_encode(x); };
-    return enc((int16_t)(a & 0xffffu)) | enc((int)a >> 16) << 8 | enc((int16_t)(b & 0xffffu)) << 16 |
-           enc((int)b >> 16) << 24;
-}
-
 // grid.x = 8 * channel groups (class = x & 7), grid.y = tiles of this launch
-// ENC: the element the store pass writes, int16 (QPSK_IN_S16) or the sample's
-// G.711 code (QPSK_IN_ALAW, QPSK_IN_ULAW: the planar formats of
+// ENC: the element the store pass writes, int16 (QPSK_OUT_S16) or the sample's
+// G.711 code (QPSK_OUT_ALAW, QPSK_OUT_ULAW: the planar formats of
 // include/qpsk_output.h).  A lane's 8 codes are one 8-byte store, and
 // (out + c * ld) mod 8 bytes repeats every 8 rows as (out + c * ld) mod 16
 // bytes does for int16, so the tiles, the classes and everything in front of
@@ -144,7 +136,7 @@ __global__ void __launch_bounds__(kThreads)
 tx_batch_kernel(const uint8_t* __restrict__ bits, const uint32_t* __restrict__ state,
                 const float2* __restrict__ tab, E* __restrict__ out, long ld, int nch, int npk, int gap,
                 int first, long tile0) {
-    static_assert(sizeof(E) == (ENC == QPSK_IN_S16 ? 2 : 1), "the element of the encoding");
+    static_assert(sizeof(E) == (ENC == QPSK_OUT_S16 ? 2 : 1), "the element of the encoding");
     __shared__ __attribute__((aligned(16))) int16_t tile[2][kTile + 2 * kMargin];
     __shared__ uint32_t sgn[kLoop][2][kSignWords];
     const int tid = threadIdx.x;
@@ -273,7 +265,7 @@ tx_batch_kernel(const uint8_t* __restrict__ bits, const uint32_t* __restrict__ s
         __syncthreads();   // one barrier per channel: the other buffer's readers passed the last one
         E* row = out + (size_t)(cbase + (long)kClasses * i) * (size_t)ld;
         const int16_t* src = buf + kMargin + tid * kChunk;
-        if constexpr (ENC == QPSK_IN_S16) {
+        if constexpr (ENC == QPSK_OUT_S16) {
             if (whole) {
                 *reinterpret_cast<uint4*>(row + p0) = *reinterpret_cast<const uint4*>(src);
             } else {
@@ -283,11 +275,11 @@ tx_batch_kernel(const uint8_t* __restrict__ bits, const uint32_t* __restrict__ s
         } else {
             if (whole) {
                 const uint4 v = *reinterpret_cast<const uint4*>(src);
-                *reinterpret_cast<uint2*>(row + p0) = make_uint2(encode4<ENC>(v.x, v.y), encode4<ENC>(v.z, v.w));
+                *reinterpret_cast<uint2*>(row + p0) = make_uint2(qfmt::encode4<ENC>(v.x, v.y), qfmt::encode4<ENC>(v.z, v.w));
             } else {
                 for (int e = 0; e < kChunk; e++)
                     if (p0 + e >= 0 && p0 + e < N)
-                        row[p0 + e] = (uint8_t)(ENC == QPSK_IN_ALAW ? qpsk_alaw_encode(src[e]) : qpsk_ulaw_encode(src[e]));
+                        row[p0 + e] = (uint8_t)qfmt::encode<ENC>(src[e]);
             }
         }
     }
@@ -408,18 +400,18 @@ extern "C" int qpsk_tx_mark(qpsk_tx_ctx* c, void* stream) {
 static int tx_check(const qpsk_tx_ctx* c, const void* bits, int npackets, const void* out, long ld) {
     if (!c || npackets < 0) return QPSK_EINVAL;
     if (npackets == 0) return QPSK_OK;
-    if (!bits || !out || (long)c->nch * npackets >= (1L << 28) ||
+    if (!bits || !out || (long)c->nch * npackets >= QPSK_TX_MAX_CHANNEL_PACKETS ||
         ld < (long)npackets * ((long)kTxPacket + c->gap))
         return QPSK_EINVAL;
     return QPSK_OK;
 }
 
 // qpsk_tx_batch_device with the element the store pass writes named: d_out is
-// int16 [nch][ld] for QPSK_IN_S16 and uint8 [nch][ld] G.711 codes for
-// QPSK_IN_ALAW / QPSK_IN_ULAW (qpsk_tx_internal.h)
+// int16 [nch][ld] for QPSK_OUT_S16 and uint8 [nch][ld] G.711 codes for
+// QPSK_OUT_ALAW / QPSK_OUT_ULAW (qpsk_tx_internal.h)
 extern "C" int qpsk_tx_batch_device_enc(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets, void* d_out,
                                         long ld, void* stream, int enc) {
-    if (enc != QPSK_IN_S16 && enc != QPSK_IN_ALAW && enc != QPSK_IN_ULAW) return QPSK_EINVAL;
+    if (enc != QPSK_OUT_S16 && enc != QPSK_OUT_ALAW && enc != QPSK_OUT_ULAW) return QPSK_EINVAL;
     const int chk = tx_check(c, d_bits, npackets, d_out, ld);
     if (chk != QPSK_OK || npackets == 0) return chk;
     hipStream_t s = (hipStream_t)stream;
@@ -450,15 +442,11 @@ extern "C" int qpsk_tx_batch_device_enc(qpsk_tx_ctx* c, const uint8_t* d_bits, i
         const unsigned gy = (unsigned)lmin(65535L, ntile - t0);
         const dim3 grid(gx, gy), block(kThreads);
         const float2* tab = c->d_tab.get();
-        if (enc == QPSK_IN_S16)
-            hipLaunchKernelGGL((tx_batch_kernel<QPSK_IN_S16, int16_t>), grid, block, 0, s, d_bits, c->d_state, tab,
-                               static_cast<int16_t*>(d_out), ld, c->nch, npackets, c->gap, first, t0);
-        else if (enc == QPSK_IN_ALAW)
-            hipLaunchKernelGGL((tx_batch_kernel<QPSK_IN_ALAW, uint8_t>), grid, block, 0, s, d_bits, c->d_state, tab,
-                               static_cast<uint8_t*>(d_out), ld, c->nch, npackets, c->gap, first, t0);
-        else
-            hipLaunchKernelGGL((tx_batch_kernel<QPSK_IN_ULAW, uint8_t>), grid, block, 0, s, d_bits, c->d_state, tab,
-                               static_cast<uint8_t*>(d_out), ld, c->nch, npackets, c->gap, first, t0);
+        qfmt::with_encoding(enc, [&](auto e) {
+            using E = std::conditional_t<e() == QPSK_OUT_S16, int16_t, uint8_t>;
+            hipLaunchKernelGGL((tx_batch_kernel<e(), E>), grid, block, 0, s, d_bits, c->d_state, tab,
+                               static_cast<E*>(d_out), ld, c->nch, npackets, c->gap, first, t0);
+        });
         HCHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(tx_state_kernel, dim3((unsigned)((c->nch + kThreads - 1) / kThreads)),
@@ -473,7 +461,7 @@ extern "C" int qpsk_tx_batch_device_enc(qpsk_tx_ctx* c, const uint8_t* d_bits, i
 
 extern "C" int qpsk_tx_batch_device(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets,
                                     int16_t* d_out, long ld, void* stream) {
-    return qpsk_tx_batch_device_enc(c, d_bits, npackets, d_out, ld, stream, QPSK_IN_S16);
+    return qpsk_tx_batch_device_enc(c, d_bits, npackets, d_out, ld, stream, QPSK_OUT_S16);
 }
 
 extern "C" int qpsk_tx_batch(qpsk_tx_ctx* c, const uint8_t* bits, int npackets, int16_t* out, long ld) {

@@ -1,5 +1,6 @@
-// qpsk_tx_internal.h -- shared between the two transmit-side translation units
-// (qpsk_synth_dev.hip, qpsk_tx.hip); not part of the public surface.
+// qpsk_tx_internal.h -- shared between the transmit-side translation units
+// (qpsk_synth_dev.hip, qpsk_tx.hip, and qpsk_output.hip for the transmitter's
+// formats); not part of the public surface.
 #pragma once
 
 #include <stddef.h>
@@ -8,6 +9,12 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+/* A packet of the batched transmitter (include/qpsk_tx.h): its transmitted
+ * samples and its payload bytes.  qpsk_tx_batch and the format entry points
+ * refuse nch * npackets from QPSK_TX_MAX_CHANNEL_PACKETS on. */
+enum { QPSK_TX_PACKET = 1880, QPSK_TX_PACKET_BITS = 496 };
+#define QPSK_TX_MAX_CHANNEL_PACKETS (1L << 28)
 
 /* The loop of qpsk_tx_phase_table() (include/qpsk_synth.h) from a carried
  * phase: ph[2] is fbb_tx_phase (re, im) before the first of these samples and,
@@ -30,8 +37,8 @@ int qpsk_tx_fmt_conv(struct qpsk_tx_ctx *c, size_t n, int16_t **p);
 int qpsk_tx_device(const struct qpsk_tx_ctx *c);
 void *qpsk_tx_host_stream(const struct qpsk_tx_ctx *c);
 /* qpsk_tx_batch_device() with the element tx_batch_kernel's store pass writes
- * named by an encoding of the format word: int16 (QPSK_IN_S16, the plain
- * call), or the sample's G.711 code (QPSK_IN_ALAW, QPSK_IN_ULAW) into d_out as
+ * named by an encoding of the format word: int16 (QPSK_OUT_S16, the plain
+ * call), or the sample's G.711 code (QPSK_OUT_ALAW, QPSK_OUT_ULAW) into d_out as
  * uint8 [nch][ld], any address: the planar G.711 formats without a pre-pass. */
 int qpsk_tx_batch_device_enc(struct qpsk_tx_ctx *c, const uint8_t *d_bits, int npackets, void *d_out,
                              long ld, void *stream, int enc);

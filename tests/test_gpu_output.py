@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = 0xC3
 GUARD = 64          # sentinel bytes between two blocks of an arena
-PATH_PREPASS, PATH_FUSED = 0, 1   # csrc/qpsk_output_internal.h QPSK_OUT_PATH_*
+PATH_PREPASS, PATH_FUSED = 0, 1   # csrc/qpsk_fmt_internal.h QPSK_OUT_PATH_*
 PLANAR_CODES = [sc.OUT_ALAW | sc.OUT_PLANAR, sc.OUT_ULAW | sc.OUT_PLANAR]
 INTERLEAVED = [sc.OUT_S16 | sc.OUT_INTERLEAVED, sc.OUT_ALAW | sc.OUT_INTERLEAVED, sc.OUT_ULAW | sc.OUT_INTERLEAVED]
 
