@@ -11,6 +11,7 @@ below comes from oracle/_ref/libqpsk_ref.so, i.e. the reference's own code.
     python tests/golden/make_golden.py --dec752   # only the dec752-mode fixtures
     python tests/golden/make_golden.py --hostile  # only hostile_ref.npz
     python tests/golden/make_golden.py --hostile-sweep   # re-choose hostile_params.json, then --hostile
+    python tests/golden/make_golden.py --spacing  # only spacing_ref.json
 
 The dec752 fixtures ("intended semantics"; NOT reference
 parity) come from oracle/_ref/libqpsk_ref752.so: the same unmodified reference
@@ -242,8 +243,29 @@ def hostile_golden():
     np.savez_compressed(os.path.join(HERE, "hostile_ref.npz"), **out)
 
 
+def spacing_golden():
+    """tests/golden/spacing_ref.json: sha256 digests of the reference's outputs
+    (both builds) over the whole corpus of tests/spacing.py, soft symbols of
+    invalid frames zeroed, and of the corpus's samples."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import spacing
+    x = spacing.corpus()
+    out = {"channels": int(x.shape[0]), "frames": int(x.shape[1]),
+           "input_sha256": hashlib.sha256(x.tobytes()).hexdigest(), "modes": {}}
+    for mode in (oracle.MODE_REF, oracle.MODE_DEC752):
+        assert oracle.ref_available(mode)
+        b, v, t = oracle.ref_rx(x, trace=True, mode=mode)
+        out["modes"][str(mode)] = spacing.digests(b, v, t)
+        print("spacing golden mode", mode, "valid", int(v.sum()), "of", v.size)
+    with open(os.path.join(HERE, "spacing_ref.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 def main():
     oracle.build(ref=True)
+    if "--spacing" in sys.argv[1:]:
+        return spacing_golden()
     if "--hostile-sweep" in sys.argv[1:]:
         hostile_sweep()
         return hostile_golden()
@@ -309,6 +331,7 @@ def main():
     print("sample:", exp["output_md5"], exp["output_bytes"], "B")
     dec752()
     hostile_golden()
+    spacing_golden()
 
 
 if __name__ == "__main__":

@@ -15,6 +15,13 @@ frames):
                and first != last maximum lag, at 26 distinct max_index;
                mode 1: 44 (22 per amplitude) at 22; every one of those frames
                valid and undecided by the filtered hunt's rule.
+
+What these corpora do not claim: the pairs (incoming rx_timing 128..255,
+max_index) on valid frames.  Every channel of the sweeps is one clocked stream
+at some delay, so of the 16,384 pairs sweep reaches 1,287 in mode 0 (1,130 in
+mode 1) and both sweeps together 1,698 (1,150); of the pairs (rx_timing of
+frame n, max_index of frame n + 1), both frames valid, 394 (220).  The plane
+is tests/spacing.py's, asserted in tests/test_spacing_corpus.py.
 """
 import numpy as np
 import pytest
