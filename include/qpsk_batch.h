@@ -44,7 +44,8 @@ enum {
     QPSK_ENODEV = -3,     /* no such HIP device */
     QPSK_EBUSY = -4,      /* qpsk_stream_acquire() with every slot in flight, or
                              qpsk_rx_reset() / qpsk_rx_state_load() on a stream's
-                             context while chunks are pending: retrieve first */
+                             context while chunks are pending: retrieve first
+                             (qpsk_rx_reset_channels / qpsk_rx_state_join alike) */
     QPSK_ESTALL = -5,     /* a device-side progress wait of rx_kernel's dual-chain
                              shapes exceeded its bound (~0.1 s): the outputs of
                              the calls since the previous check are undefined.
@@ -100,7 +101,8 @@ uint64_t qpsk_rx_frames(const qpsk_ctx *ctx);
  * (src/scramble.c:41-42, a function of the frame index).  The context holds
  * the equivalent per channel in device memory: the history of the last two
  * frames, the next frame's equalizer window (dec[mi .. mi+166]) with its
- * preamble position, and rx_timing; the frame index is the context's.
+ * preamble position, and rx_timing; the frame index is the channel's own
+ * (the context's, unless the channel was reset or joined on its own, below).
  *
  *   qpsk_rx_state_size(n)        bytes of a snapshot of n channels
  *   qpsk_rx_state_save(ctx, c0, n, buf, size)
@@ -108,14 +110,16 @@ uint64_t qpsk_rx_frames(const qpsk_ctx *ctx);
  *   qpsk_rx_state_load(ctx, c0, n, buf, size)
  *                                buf -> channels [c0, c0 + n) of ctx
  *
- * A snapshot records the context's mode and frame index.  Loading it into a
+ * A snapshot records the context's mode and its channels' frame index.  Loading it into a
  * context of the same mode (on any device, in any process) continues those
  * channels exactly where they stopped: demodulating 7 frames, saving,
  * loading into a fresh context and demodulating 9 more gives the outputs of
- * one 16-frame call.  The frame index is shared by all channels of a
- * context: a context takes the snapshot's index when it has received no
- * frame since create/reset (qpsk_rx_frames() == 0); otherwise the indices
- * must be equal (QPSK_EINVAL).  Loading fewer than all channels into such a
+ * one 16-frame call.  qpsk_rx_state_load keeps the loaded channels on the
+ * context's own frame index: a context takes the snapshot's index when it has
+ * received no frame since create/reset (qpsk_rx_frames() == 0); otherwise the
+ * indices must be equal (QPSK_EINVAL).  (Every channel has a frame index of
+ * its own, qpsk_rx_channel_frames below; qpsk_rx_state_join loads a snapshot
+ * at any index into a context at any other.)  Loading fewer than all channels into such a
  * fresh context from a snapshot at frame G != 0 moves every channel to frame
  * G, so the context then receives nothing (qpsk_rx_batch*, streams, state
  * saves: QPSK_EINVAL) until each of its channels has been loaded from
@@ -174,6 +178,42 @@ const char *qpsk_strerror(int err);
  * (singlecarrier_amd/csrc/Makefile KSRC, KCMD).  Profiled counters record it;
  * bench.py reports them only for a library with the same hash. */
 const char *qpsk_kernel_hash(void);
+
+/* Channels that come and go (INTEGRATION.md "Channels that come and go").
+ * Every channel has a frame index of its own: the number of frames of its
+ * current stream it has received, 64-bit.  It is the context's
+ * (qpsk_rx_frames) until one of the calls below gives the channel another
+ * start; from then on both advance together, and every channel still behaves
+ * exactly like a fresh run of the reference receiver fed that channel's stream
+ * from its start.  Contexts that never use these calls are as before.
+ *
+ *   qpsk_rx_reset_channels(ctx, c0, n)
+ *       channels [c0, c0 + n) back to the reference's initial RX state, at own
+ *       index 0; every other channel is untouched.  Waits for the context's
+ *       calls in flight.  QPSK_EBUSY on a stream's context while chunks are
+ *       pending; QPSK_EINVAL for a range outside the context or while channels
+ *       are still to be loaded (qpsk_rx_state_load's assembly); QPSK_ESTALL on
+ *       a context that has stalled, which only qpsk_rx_reset recovers.
+ *   qpsk_rx_channel_frames(ctx, c0, n, out)
+ *       out[i] = the own frame index of channel c0 + i.  qpsk_rx_frames() stays
+ *       the context's count of frames per channel since create / reset / load.
+ *   qpsk_rx_state_join(ctx, c0, n, buf, size)
+ *       qpsk_rx_state_load without its frame-index rule and without the
+ *       assembly hold: the snapshot's channels go into channels [c0, c0 + n) of
+ *       a context at any frame index and continue there at the snapshot's,
+ *       while the others go on.  Same checks and errors otherwise; QPSK_EINVAL
+ *       while channels are still to be loaded.
+ *
+ * qpsk_rx_state_save writes the range's own index into the snapshot and
+ * returns QPSK_EINVAL when the channels of the range do not share one.  A
+ * snapshot does not depend on the context it was taken from: a range that was
+ * reset or joined on its own gives the bytes that the same channels, fed the
+ * same frames, give in a context that never used these calls.
+ * qpsk_rx_state_load keeps its rules, stated over the context's index, and
+ * leaves the loaded channels counting with the context. */
+int qpsk_rx_reset_channels(qpsk_ctx *ctx, int c0, int n);
+int qpsk_rx_channel_frames(const qpsk_ctx *ctx, int c0, int n, uint64_t *out);
+int qpsk_rx_state_join(qpsk_ctx *ctx, int c0, int n, const void *buf, size_t size);
 
 #ifdef __cplusplus
 }

@@ -151,6 +151,9 @@ def lib():
         L.qpsk_rx_state_size.argtypes = [i32]
         L.qpsk_rx_state_save.argtypes = [vp, i32, i32, vp, C.c_size_t]
         L.qpsk_rx_state_load.argtypes = [vp, i32, i32, vp, C.c_size_t]
+        L.qpsk_rx_state_join.argtypes = [vp, i32, i32, vp, C.c_size_t]
+        L.qpsk_rx_reset_channels.argtypes = [vp, i32, i32]
+        L.qpsk_rx_channel_frames.argtypes = [vp, i32, i32, vp]
         L.qpsk_tx_create.restype = vp
         L.qpsk_tx_create.argtypes = [i32, i32, i32, C.POINTER(C.c_int)]
         L.qpsk_tx_destroy.restype = None
@@ -206,6 +209,7 @@ SYMBOLS = ["qpsk_rx_create", "qpsk_rx_create_mode", "qpsk_rx_mode", "qpsk_rx_des
            "qpsk_stream_retrieve", "qpsk_stream_ctx", "qpsk_records", "qpsk_fft_alloc",
            "qpsk_fft_free", "qpsk_fft_device", "qpsk_fft", "qpsk_rx_state_size",
            "qpsk_rx_state_save", "qpsk_rx_state_load",
+           "qpsk_rx_state_join", "qpsk_rx_reset_channels", "qpsk_rx_channel_frames",
            "qpsk_tx_create", "qpsk_tx_destroy", "qpsk_tx_reset", "qpsk_tx_channels", "qpsk_tx_gap",
            "qpsk_tx_packets", "qpsk_tx_batch", "qpsk_tx_batch_device", "qpsk_tx_sync",
            "qpsk_tx_batch_host",
@@ -508,15 +512,41 @@ class Receiver:
         _check(lib().qpsk_rx_state_save(self._h, c0, n, _ptr(buf), buf.size))
         return buf.tobytes()
 
-    def state_load(self, snap: bytes, c0: int = 0, n: int | None = None) -> None:
-        """Load a snapshot of n channels into channels [c0, c0 + n)
-        (qpsk_rx_state_load)."""
+    @staticmethod
+    def _snapshot(snap: bytes, n):
+        """(buffer, n) of a snapshot: length and magic checked before its header is read."""
         buf = np.frombuffer(snap, np.uint8)
         if len(snap) < 64 or bytes(snap[:8]) != b"QPSKSTA1":   # StateHdr: 64 bytes, magic first
             _check(QPSK_EINVAL)
         if n is None:
             n = int(np.frombuffer(snap[20:24], np.int32)[0])   # StateHdr.n
+        return buf, n
+
+    def state_load(self, snap: bytes, c0: int = 0, n: int | None = None) -> None:
+        """Load a snapshot of n channels into channels [c0, c0 + n)
+        (qpsk_rx_state_load)."""
+        buf, n = self._snapshot(snap, n)
         _check(lib().qpsk_rx_state_load(self._h, c0, n, _ptr(buf), buf.size))
+
+    def state_join(self, snap: bytes, c0: int = 0, n: int | None = None) -> None:
+        """Load a snapshot of n channels, taken at any frame index, into
+        channels [c0, c0 + n) while the others go on: the joined channels
+        continue at the snapshot's index (qpsk_rx_state_join)."""
+        buf, n = self._snapshot(snap, n)
+        _check(lib().qpsk_rx_state_join(self._h, c0, n, _ptr(buf), buf.size))
+
+    def reset_channels(self, c0: int, n: int = 1) -> None:
+        """Channels [c0, c0 + n) back to their initial state, at own frame index
+        0; every other channel is untouched (qpsk_rx_reset_channels)."""
+        _check(lib().qpsk_rx_reset_channels(self._h, c0, n))
+
+    def channel_frames(self, c0: int = 0, n: int | None = None) -> np.ndarray:
+        """The own frame index of channels [c0, c0 + n), uint64 [n]
+        (qpsk_rx_channel_frames); ``frames`` stays the context's."""
+        n = self.nch - c0 if n is None else n
+        out = np.zeros(max(n, 0), np.uint64)
+        _check(lib().qpsk_rx_channel_frames(self._h, c0, n, _ptr(out)))
+        return out
 
     def timing(self, on: bool = True) -> None:
         """Enable per-call step-kernel span events (see qpsk_rx_timing_collect)."""

@@ -612,7 +612,7 @@ int qpsk_rx_launch_kernels(const RxLaunch& a) {
     const unsigned ncarry = (unsigned)std::min(kCarryGrid, (a.nch + kPerBlock - 1) / kPerBlock);
     const int head8 = (a.mode & QPSK_MODE_DEC752) ? 213 : 149;   // x_{F-1}[0..1704) or [0..1192)
     hipLaunchKernelGGL(rx_data_kernel, dim3(ncarry + dgrid), dim3(kDataBlock), 0, a.s, a.jobs,
-                       (unsigned long long)a.jobs_cap, a.njobs, a.ks, a.bits,
+                       (unsigned long long)a.jobs_cap, a.njobs, a.ks, a.koff, a.bits,
                        reinterpret_cast<float2*>(a.soft), a.parity, a.roles & kForceExact, a.ctx_err,
                        a.err_to, a.in, a.hist, a.nch, a.F, head8, ncarry);
     HCHECK(hipGetLastError());

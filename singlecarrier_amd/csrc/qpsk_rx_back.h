@@ -457,10 +457,13 @@ __device__ __forceinline__ void carry_block(const int16_t* in, int16_t* hist, in
 // nearly idle, so the copy runs beside them.  The call's rx_kernel, which reads
 // the history for its first frame, is done (stream order), and the next
 // call's comes after this launch.
+// The descrambler word is the one place where a frame's index shows in the
+// outputs, and it is applied here: a job carries the word of the call's own
+// frame index (j.ks), and koff[channel] moves it to the channel's.
 __global__ void __launch_bounds__(256) rx_data_kernel(const float4* jobs, unsigned long long jcap,
                                                       unsigned* njobs,
                                                       const unsigned long long* ks_tab,
-                                                      uint8_t* bits, float2* soft, int parity,
+                                                      const unsigned* koff, uint8_t* bits, float2* soft, int parity,
                                                       int force_exact, int* err, int* err_to,
                                                       const int16_t* in, int16_t* hist, int nch, int F,
                                                       int head8, unsigned ncarry) {
@@ -492,7 +495,12 @@ __global__ void __launch_bounds__(256) rx_data_kernel(const float4* jobs, unsign
         f2 x[5];
 #pragma unroll
         for (int t = 0; t < 5; t++) x[t] = xs[t];
-        const unsigned long long ks = ks_tab[j.ks];
+        // the channel's own frame index, koff[ch] frames ahead of the call's
+        // (mod 1057; zero unless the channel was reset or joined on its own):
+        // ch = cf / F, 32-bit (cf < 2^28, qpsk_rx_launch)
+        unsigned kw = j.ks + koff[(unsigned)j.cf / (unsigned)F];
+        if (kw >= (unsigned)QK_KS_FRAMES) kw -= (unsigned)QK_KS_FRAMES;
+        const unsigned long long ks = ks_tab[kw];
         float2* so = soft ? soft + j.cf * QK_NDSYM : nullptr;
         bool bad = force_exact != 0;
         unsigned long long dib = data_steps<false>(j.k, x, xs, so, bad);

@@ -83,7 +83,9 @@ namespace {
 // (the next frame): the history int16 [2][1880] (frames G-2, G-1:
 // carry_block), window G's row float2 [168] with mi_G, and rt_G, the last
 // three in the arrays of parity G & 1 (rx_kernel reads mi_of / rt_of / win_of
-// (g0) at a call's start and writes parity g0 + F at its end).
+// (g0) at a call's start and writes parity g0 + F at its end).  koff: what
+// the channel's own frame index is ahead of the context's, mod 1057 (rx_koff,
+// qpsk_rx_plan.h); rx_data_kernel descrambles with it.
 struct ChanState {
     size_t ns = 0;
     qhip::DevBuf<float2> ptab;
@@ -92,27 +94,51 @@ struct ChanState {
     qhip::DevBuf<int16_t> hist;
     qhip::DevBuf<float2> win[2];
     qhip::DevBuf<int> mi[2], rt[2];
+    qhip::DevBuf<unsigned> koff;
 
-    // every channel as before its first frame; the memsets are left on s
+    // every channel as before its first frame, counting with the context; the
+    // memsets are left on s
     int reset(hipStream_t s) {
-        HCHECK(hipMemsetAsync(hist, 0, sizeof(int16_t) * ns * 2 * QK_FRAME, s));
+        HCHECK(hipMemsetAsync(koff, 0, sizeof(unsigned) * ns, s));
+        return reset_slots(0, ns, s);
+    }
+
+    // slots [c0, c0 + n) as before their first frame (koff is the caller's);
+    // the memsets are left on s
+    int reset_slots(size_t c0, size_t n, hipStream_t s) {
+        HCHECK(hipMemsetAsync(hist + c0 * 2 * QK_FRAME, 0, sizeof(int16_t) * n * 2 * QK_FRAME, s));
         for (int p = 0; p < 2; p++) {
-            HCHECK(hipMemsetAsync(win[p], 0, sizeof(float2) * ns * kWinStride, s));
-            HCHECK(hipMemsetAsync(mi[p], 0, sizeof(int) * ns, s));
+            HCHECK(hipMemsetAsync(win[p] + c0 * kWinStride, 0, sizeof(float2) * n * kWinStride, s));
+            HCHECK(hipMemsetAsync(mi[p] + c0, 0, sizeof(int) * n, s));
         }
-        int* rt0 = (int*)malloc(sizeof(int) * ns);
+        int* rt0 = (int*)malloc(sizeof(int) * n);
         if (!rt0) return QPSK_ENOMEM;
-        for (size_t i = 0; i < ns; i++) rt0[i] = QK_RT0;
-        hipError_t e = hipMemcpy(rt[0], rt0, sizeof(int) * ns, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(rt[1], rt0, sizeof(int) * ns, hipMemcpyHostToDevice);
+        for (size_t i = 0; i < n; i++) rt0[i] = QK_RT0;
+        hipError_t e = hipMemcpy(rt[0] + c0, rt0, sizeof(int) * n, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(rt[1] + c0, rt0, sizeof(int) * n, hipMemcpyHostToDevice);
         free(rt0);
         return herr(e);
     }
 
+    // koff of channels [c0, c0 + n) = v, on s (synchronised before it returns:
+    // the source is pageable)
+    int set_koff(size_t c0, size_t n, unsigned v, hipStream_t s) {
+        if (v == 0) {
+            HCHECK(hipMemsetAsync(koff + c0, 0, sizeof(unsigned) * n, s));
+            return QPSK_OK;
+        }
+        std::vector<unsigned> h(n, v);
+        HCHECK(hipMemcpyAsync(koff + c0, h.data(), sizeof(unsigned) * n, hipMemcpyHostToDevice, s));
+        HCHECK(hipStreamSynchronize(s));
+        return QPSK_OK;
+    }
+
     // A snapshot's body (qpsk_rx_plan.h: the four fields channel-major, each
     // one block) of channels [c0, c0 + n) at parity p, to the host (kind
-    // hipMemcpyDeviceToHost) or from it, on s
-    int copy(char* host, int c0, size_t n, int p, hipMemcpyKind kind, hipStream_t s) {
+    // hipMemcpyDeviceToHost) or from it, on s; to the device, the window rows
+    // may come from another host block (win_from, n rows)
+    int copy(char* host, int c0, size_t n, int p, hipMemcpyKind kind, hipStream_t s,
+             const char* win_from = nullptr) {
         auto field = [&](void* dev, size_t bytes) {
             const bool out = kind == hipMemcpyDeviceToHost;
             const hipError_t e = hipMemcpyAsync(out ? (void*)host : dev, out ? dev : (void*)host, bytes, kind, s);
@@ -120,7 +146,12 @@ struct ChanState {
             return e;
         };
         HCHECK(field(hist + (size_t)c0 * 2 * QK_FRAME, n * kHistB));
-        HCHECK(field(win[p] + (size_t)c0 * kWinStride, n * kWinB));
+        if (win_from) {
+            HCHECK(hipMemcpyAsync(win[p] + (size_t)c0 * kWinStride, win_from, n * kWinB, kind, s));
+            host += n * kWinB;
+        } else {
+            HCHECK(field(win[p] + (size_t)c0 * kWinStride, n * kWinB));
+        }
         HCHECK(field(mi[p] + c0, n * sizeof(int)));
         HCHECK(field(rt[p] + c0, n * sizeof(int)));
         return QPSK_OK;
@@ -261,6 +292,9 @@ struct qpsk_ctx {
     SpanTimer spans;
     RxKnobs knobs;
     Assembly assembly;
+    // per channel: its own frame index minus `frames`, wrapped (rx_index_lead,
+    // qpsk_rx_plan.h); all zero unless qpsk_rx_reset_channels / qpsk_rx_state_join
+    std::vector<uint64_t> lead;
     qhip::DevBuf<int> d_err;    // [0] device error word (kErrStall), taken by qpsk_rx_sync;
                                 // [1] the value it took
     qhip::Event done;           // recorded after the latest call's kernels, on its stream
@@ -294,6 +328,7 @@ extern "C" int qpsk_rx_reset(qpsk_ctx* c) {
     c->epoch++;
     c->stalled = false;
     c->assembly = Assembly{};
+    c->lead.assign((size_t)c->nch, 0);
     return QPSK_OK;
 }
 
@@ -383,6 +418,7 @@ static int ctx_alloc(qpsk_ctx* c) {
         HCHECK(st.mi[p].reserve(st.ns));
         HCHECK(st.rt[p].reserve(st.ns));
     }
+    HCHECK(st.koff.reserve(st.ns));   // (after the arrays above: they stay where they were)
     const RxTables& t = rx_tables();
     HCHECK(hipMemcpy(st.ptab, t.ptab, sizeof t.ptab, hipMemcpyHostToDevice));
     HCHECK(hipMemcpy(st.ks, t.ksf, sizeof t.ksf, hipMemcpyHostToDevice));
@@ -411,6 +447,7 @@ static int ctx_init(qpsk_ctx* c) {
     l.hist = c->st.hist;
     l.ptab = c->st.ptab;
     l.ks = c->st.ks;
+    l.koff = c->st.koff;
     for (int p = 0; p < 2; p++) {
         l.win[p] = c->st.win[p];
         l.mi[p] = c->st.mi[p];
@@ -459,27 +496,50 @@ static int state_begin(qpsk_ctx* c, int c0, int n, const void* buf, size_t size)
     return QPSK_OK;
 }
 
-extern "C" int qpsk_rx_state_save(qpsk_ctx* c, int c0, int n, void* buf, size_t size) {
-    int r = state_begin(c, c0, n, buf, size);
-    if (r != QPSK_OK) return r;
-    // channels still to be loaded (qpsk_rx_state_load) hold no state of frame G
-    if (c->assembly.left > 0) return QPSK_EINVAL;
-    // a stall (reported, or still in the error word: peeked, not taken, so
-    // qpsk_rx_sync still reports it) leaves the state undefined
+// A stall (reported, or still in the error word: peeked, not taken, so
+// qpsk_rx_sync still reports it) leaves every channel's state undefined:
+// QPSK_ESTALL then.  (The context's calls in flight have been waited for.)
+static int state_defined(qpsk_ctx* c) {
     if (!c->stalled) {
         int e = 0;
         HCHECK(hipMemcpyAsync(&e, c->d_err, sizeof e, hipMemcpyDeviceToHost, c->stream));
         HCHECK(hipStreamSynchronize(c->stream));
         if (e != 0) return QPSK_ESTALL;
     }
-    if (c->stalled) return QPSK_ESTALL;
+    return c->stalled ? QPSK_ESTALL : QPSK_OK;
+}
+
+// n window rows (kWinB bytes each) negated in place: what the rows of a
+// channel are in a context whose frame index differs from the channel's own by
+// an odd number (rx_lead_odd, qpsk_rx_plan.h).  Zeros keep their sign: sums of
+// the FIR that cancel exactly are +0 under either mixer sign.
+static void negate_windows(char* w, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+        uint32_t* f = reinterpret_cast<uint32_t*>(w + i * kWinB);
+        for (int k = 0; k < 2 * kWinObs; k++)
+            if ((f[k] & 0x7fffffffu) != 0) f[k] ^= 0x80000000u;
+    }
+}
+
+extern "C" int qpsk_rx_state_save(qpsk_ctx* c, int c0, int n, void* buf, size_t size) {
+    int r = state_begin(c, c0, n, buf, size);
+    if (r != QPSK_OK) return r;
+    // channels still to be loaded (qpsk_rx_state_load) hold no state of frame G
+    if (c->assembly.left > 0) return QPSK_EINVAL;
+    r = state_defined(c);
+    if (r != QPSK_OK) return r;
+    // a snapshot has one frame index: the range's own
+    const uint64_t lead = c->lead[(size_t)c0];
+    for (int i = c0; i < c0 + n; i++)
+        if (c->lead[(size_t)i] != lead) return QPSK_EINVAL;
+    const uint64_t own = rx_own_index(c->frames, lead);
     StateHdr h{};
     memcpy(h.magic, kStateMagic, sizeof h.magic);
     h.version = 1;
     h.hdr_bytes = sizeof h;
     h.mode = c->mode;
     h.n = n;
-    h.frame = c->frames;
+    h.frame = own;
     h.hist_bytes = (uint32_t)kHistB;
     h.win_bytes = (uint32_t)kWinB;
     char* o = static_cast<char*>(buf);
@@ -496,6 +556,16 @@ extern "C" int qpsk_rx_state_save(qpsk_ctx* c, int c0, int n, void* buf, size_t 
     char* w = o + nn * kHistB;
     for (size_t i = 0; i < nn; i++)
         memset(w + i * kWinB + kWinObs * sizeof(float2), 0, (kWinStride - kWinObs) * sizeof(float2));
+    if (rx_lead_odd(own, c->frames)) negate_windows(w, nn);   // the channels' own convention
+    return QPSK_OK;
+}
+
+// a snapshot's header, checked against the context and the range it goes to
+static int state_header(const qpsk_ctx* c, int n, const void* buf, StateHdr* h) {
+    memcpy(h, buf, sizeof *h);
+    if (memcmp(h->magic, kStateMagic, sizeof h->magic) != 0 || h->version != 1 || h->hdr_bytes != sizeof *h ||
+        h->n != n || h->mode != c->mode || h->hist_bytes != kHistB || h->win_bytes != kWinB)
+        return QPSK_EINVAL;
     return QPSK_OK;
 }
 
@@ -503,11 +573,10 @@ extern "C" int qpsk_rx_state_load(qpsk_ctx* c, int c0, int n, const void* buf, s
     int r = state_begin(c, c0, n, buf, size);
     if (r != QPSK_OK) return r;
     StateHdr h;
-    memcpy(&h, buf, sizeof h);
-    if (memcmp(h.magic, kStateMagic, sizeof h.magic) != 0 || h.version != 1 || h.hdr_bytes != sizeof h ||
-        h.n != n || h.mode != c->mode || h.hist_bytes != kHistB || h.win_bytes != kWinB)
-        return QPSK_EINVAL;
-    if (c->frames != h.frame && c->frames != 0) return QPSK_EINVAL;   // one frame index per context
+    r = state_header(c, n, buf, &h);
+    if (r != QPSK_OK) return r;
+    // the context's index or a fresh context (qpsk_rx_state_join takes any)
+    if (c->frames != h.frame && c->frames != 0) return QPSK_EINVAL;
     // a channel range at frame G != 0 into a fresh context moves the context's
     // frame index to G for every channel: the others must be loaded too
     // (from this or other snapshots at G) before the context may receive
@@ -522,6 +591,10 @@ extern "C" int qpsk_rx_state_load(qpsk_ctx* c, int c0, int n, const void* buf, s
         if (a.cover.empty()) {
             a.cover.assign((size_t)c->nch, 0);
             a.left = c->nch;
+            // every channel moves to the snapshot's index with the context
+            c->lead.assign((size_t)c->nch, 0);
+            HCHECK(hipMemsetAsync(c->st.koff, 0, sizeof(unsigned) * c->st.ns, c->stream));
+            HCHECK(hipStreamSynchronize(c->stream));
         }
         for (int i = c0; i < c0 + n; i++)
             if (!a.cover[(size_t)i]) {
@@ -530,7 +603,67 @@ extern "C" int qpsk_rx_state_load(qpsk_ctx* c, int c0, int n, const void* buf, s
             }
         if (a.left == 0) a.cover.clear();
     }
+    // the loaded channels count with the context
+    r = c->st.set_koff((size_t)c0, (size_t)n, 0, c->stream);
+    if (r != QPSK_OK) return r;
+    HCHECK(hipStreamSynchronize(c->stream));
+    for (int i = c0; i < c0 + n; i++) c->lead[(size_t)i] = 0;
     c->frames = h.frame;
+    return QPSK_OK;
+}
+
+extern "C" int qpsk_rx_state_join(qpsk_ctx* c, int c0, int n, const void* buf, size_t size) {
+    int r = state_begin(c, c0, n, buf, size);
+    if (r != QPSK_OK) return r;
+    // (a context under assembly has no frame index to join at yet)
+    if (c->assembly.left > 0) return QPSK_EINVAL;
+    StateHdr h;
+    r = state_header(c, n, buf, &h);
+    if (r != QPSK_OK) return r;
+    const char* o = static_cast<const char*>(buf) + sizeof h;
+    const size_t nn = (size_t)n;
+    // the state of the channels' next frame goes where the context's next
+    // frame reads it: its current parity.  The snapshot's rows are in the
+    // channels' own convention (qpsk_rx_state_save).
+    std::vector<char> win;
+    if (rx_lead_odd(h.frame, c->frames)) {
+        win.assign(o + nn * kHistB, o + nn * (kHistB + kWinB));
+        negate_windows(win.data(), nn);
+    }
+    r = c->st.copy(const_cast<char*>(o), c0, nn, (int)(c->frames & 1u), hipMemcpyHostToDevice, c->stream,
+                   win.empty() ? nullptr : win.data());
+    if (r != QPSK_OK) return r;
+    r = c->st.set_koff((size_t)c0, nn, rx_koff(h.frame, c->frames), c->stream);
+    if (r != QPSK_OK) return r;
+    HCHECK(hipStreamSynchronize(c->stream));
+    for (int i = c0; i < c0 + n; i++) c->lead[(size_t)i] = rx_index_lead(h.frame, c->frames);
+    return QPSK_OK;
+}
+
+extern "C" int qpsk_rx_reset_channels(qpsk_ctx* c, int c0, int n) {
+    if (!c || n < 1 || c0 < 0 || c0 > c->nch - n) return QPSK_EINVAL;
+    if (c->owner && qpsk_stream_pending(c->owner) > 0) return QPSK_EBUSY;
+    // channels of a context under assembly hold no state to go on beside
+    if (c->assembly.left > 0) return QPSK_EINVAL;
+    HCHECK(hipSetDevice(c->device));
+    // calls in flight read and write the state cleared here
+    if (c->called) HCHECK(hipEventSynchronize(c->done));
+    // a stall leaves every channel undefined and the context's epoch open:
+    // only qpsk_rx_reset recovers it
+    int r = state_defined(c);
+    if (r != QPSK_OK) return r;
+    r = c->st.reset_slots((size_t)c0, (size_t)n, c->stream);
+    if (r != QPSK_OK) return r;
+    r = c->st.set_koff((size_t)c0, (size_t)n, rx_koff(0, c->frames), c->stream);
+    if (r != QPSK_OK) return r;
+    HCHECK(hipStreamSynchronize(c->stream));
+    for (int i = c0; i < c0 + n; i++) c->lead[(size_t)i] = rx_index_lead(0, c->frames);
+    return QPSK_OK;
+}
+
+extern "C" int qpsk_rx_channel_frames(const qpsk_ctx* c, int c0, int n, uint64_t* out) {
+    if (!c || !out || n < 1 || c0 < 0 || c0 > c->nch - n) return QPSK_EINVAL;
+    for (int i = 0; i < n; i++) out[i] = rx_own_index(c->frames, c->lead[(size_t)(c0 + i)]);
     return QPSK_OK;
 }
 

@@ -120,6 +120,28 @@ static_assert(kWinObs == 164 && kWinObs <= kWinStride, "window slots");
 
 inline size_t rx_state_size(int n) { return n < 1 ? 0 : sizeof(StateHdr) + (size_t)n * kChanB; }
 
+// ---------------------------------------------------------------- channel frame index
+// A channel that was reset or joined on its own (qpsk_rx_reset_channels,
+// qpsk_rx_state_join) counts its frames from another start than its context.
+// The host keeps, per channel, lead = own index - context's index as a wrapped
+// 64-bit difference: both advance together, so it changes only in those calls.
+// Exact for any two indices below 2^64.
+inline uint64_t rx_index_lead(uint64_t own, uint64_t ctx) { return own - ctx; }
+inline uint64_t rx_own_index(uint64_t ctx, uint64_t lead) { return ctx + lead; }
+// What the data kernel adds to a job's descrambler word (koff, qpsk_rx_back.h):
+// (own - ctx) mod 1057 in [0, 1057), from the two residues -- not from the
+// wrapped difference, since 2^64 mod 1057 != 0.
+inline unsigned rx_koff(uint64_t own, uint64_t ctx) {
+    const unsigned a = (unsigned)(own % (uint64_t)QK_KS_FRAMES), b = (unsigned)(ctx % (uint64_t)QK_KS_FRAMES);
+    return a >= b ? a - b : a + (unsigned)QK_KS_FRAMES - b;
+}
+// The mixer sign and the state parity stay the context's for every channel
+// (negating a channel's mixed samples changes no output), so a
+// channel whose lead is odd holds its window row negated with respect to a
+// context that counts as the channel does.  Snapshots are written in the
+// channel's own convention: save and join negate the row when this is true.
+inline bool rx_lead_odd(uint64_t own, uint64_t ctx) { return ((own ^ ctx) & 1u) != 0; }
+
 // state arrays cover whole workgroups of the largest shape (kMaxGroups groups)
 inline size_t rx_nslot(int nch) {
     const int ngroup = (nch + QK_GROUP - 1) / QK_GROUP;

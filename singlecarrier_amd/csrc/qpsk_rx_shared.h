@@ -92,6 +92,7 @@ struct RxLaunch {
     int16_t* hist;
     const float2* ptab;
     const unsigned long long* ks;
+    const unsigned* koff;    // [nslot] per channel: (own frame index - the context's) mod 1057
     float2* win[2];
     int* mi[2];
     int* rt[2];
