@@ -9,6 +9,14 @@
  *
  *   qpsk_rx_stream [-f FRAMES_PER_CHUNK] [-f FMT] in1.raw [in2.raw ...] -o PREFIX
  *   qpsk_rx_stream [-f FRAMES_PER_CHUNK] [-f FMT] -i NCH trunk.raw -o PREFIX
+ *   qpsk_rx_stream ... -p FILE      (in place of -o PREFIX)
+ *
+ * -p FILE: one file of 16-byte records (qpsk_frame_rec, include/qpsk_compact.h:
+ * channel, frame, the 62 bits in one word) of all channels in time order,
+ * instead of the per-channel files: the stream is one of records in by-frame
+ * order (qpsk_stream_create_records), only the valid frames cross PCIe, and a
+ * record's frame is its position in the whole stream (the chunk's first frame
+ * added).
  *
  * FMT = s16 (default), alaw or ulaw: the files hold 8-bit G.711 codes, which go
  * into the pinned slots and over PCIe as they are and are expanded on the GPU
@@ -24,6 +32,7 @@
 #include <string.h>
 
 #include "qpsk_batch.h"
+#include "qpsk_compact.h"
 #include "qpsk_input.h"
 #include "qpsk_internal.h"
 #include "qpsk_stream.h"
@@ -42,9 +51,27 @@ static void drain(qpsk_stream *s, int nch, int frames, int nf_chunk, FILE **out,
     }
 }
 
+/* a chunk of a record stream: the records of its first nf_chunk frames (by-frame
+ * order: the first groups[nf_chunk] of them), at first_frame of the stream */
+static void drain_records(qpsk_stream *s, int nf_chunk, long first_frame, FILE *out) {
+    const qpsk_frame_rec *rec;
+    const uint32_t *groups;
+    uint32_t count;
+    int err = qpsk_stream_retrieve_records(s, &rec, &count, &groups);
+    if (err) {
+        fprintf(stderr, "qpsk: %s\n", qpsk_strerror(err));
+        exit(3);
+    }
+    for (uint32_t k = 0; k < groups[nf_chunk]; k++) {
+        qpsk_frame_rec r = rec[k];
+        r.frame += (uint32_t)first_frame;
+        if (fwrite(&r, sizeof r, 1, out) != 1) exit(1);
+    }
+}
+
 static void usage(const char *argv0) {
     fprintf(stderr, "usage: %s [-f FRAMES_PER_CHUNK] [-f s16|alaw|ulaw] (in1.raw [in2.raw ...] | -i NCH trunk.raw) "
-                    "-o PREFIX\n", argv0);
+                    "(-o PREFIX | -p FILE)\n", argv0);
 }
 
 int main(int argc, char **argv) {
@@ -58,7 +85,8 @@ int main(int argc, char **argv) {
         else frames = atoi(v);
         a += 2;
     }
-    if (argc - a < 3 || strcmp(argv[argc - 2], "-o") || frames < 1 || trunk < 0 || (trunk && argc - a != 3)) {
+    const int packed = argc >= 2 && !strcmp(argv[argc - 2], "-p");
+    if (argc - a < 3 || (!packed && strcmp(argv[argc - 2], "-o")) || frames < 1 || trunk < 0 || (trunk && argc - a != 3)) {
         usage(argv[0]);
         return 2;
     }
@@ -67,17 +95,22 @@ int main(int argc, char **argv) {
     if (trunk) fmt |= QPSK_IN_INTERLEAVED;
     const char *prefix = argv[argc - 1];
     FILE **in = calloc((size_t)nfile, sizeof(FILE *)), **out = calloc((size_t)nch, sizeof(FILE *));
+    FILE *pout = packed ? fopen(prefix, "wb") : NULL;
+    if (packed && !pout) return 1;
     for (int c = 0; c < nch; c++) {
         char name[4096];
         snprintf(name, sizeof name, "%s%d.bin", prefix, c);
         if (c < nfile && !(in[c] = fopen(argv[a + c], "rb"))) return 1;
+        if (packed) continue;
         out[c] = fopen(name, "wb");
         if (!out[c]) return 1;
     }
     const int nslot = 3;
     int err;
     /* (planar int16 is the plain stream: qpsk_stream_create) */
-    qpsk_stream *s = qpsk_stream_create_fmt(0, nch, frames, nslot, QPSK_MODE_REFERENCE, fmt, &err);
+    qpsk_stream *s = packed ? qpsk_stream_create_records(0, nch, frames, nslot, QPSK_MODE_REFERENCE, fmt,
+                                                         QPSK_REC_BY_FRAME, (size_t)nch * (size_t)frames, &err)
+                            : qpsk_stream_create_fmt(0, nch, frames, nslot, QPSK_MODE_REFERENCE, fmt, &err);
     if (!s) {
         fprintf(stderr, "qpsk: %s\n", qpsk_strerror(err));
         return 3;
@@ -87,7 +120,8 @@ int main(int argc, char **argv) {
     long submitted = 0, retrieved = 0;
     for (int done = 0; !done;) {
         if (qpsk_stream_pending(s) == nslot) {
-            drain(s, nch, frames, sizes[retrieved % nslot], out, rec);
+            if (packed) drain_records(s, sizes[retrieved % nslot], retrieved * frames, pout);
+            else drain(s, nch, frames, sizes[retrieved % nslot], out, rec);
             retrieved++;
         }
         char *buf = qpsk_stream_acquire_raw(s, &err);
@@ -117,14 +151,16 @@ int main(int argc, char **argv) {
         submitted++;
     }
     while (retrieved < submitted) {
-        drain(s, nch, frames, sizes[retrieved % nslot], out, rec);
+        if (packed) drain_records(s, sizes[retrieved % nslot], retrieved * frames, pout);
+        else drain(s, nch, frames, sizes[retrieved % nslot], out, rec);
         retrieved++;
     }
     qpsk_stream_destroy(s);
     for (int c = 0; c < nch; c++) {
         if (c < nfile) fclose(in[c]);
-        fclose(out[c]);
+        if (out[c]) fclose(out[c]);
     }
+    if (pout) fclose(pout);
     free(rec);
     return 0;
 }

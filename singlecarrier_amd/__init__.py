@@ -4,7 +4,9 @@ Python mirror of the C-ABI in ``include/qpsk_internal.h`` (the reference's
 ``headers/qpsk_internal.h:79-84`` surface) and ``include/qpsk_batch.h`` (the
 batched, multi-channel receiver), ``include/qpsk_tx.h`` (the batched
 transmitter), ``include/qpsk_input.h`` (G.711 and timeslot-interleaved
-input) and ``include/qpsk_output.h`` (the same formats as output), over ``singlecarrier_amd/libqpsk_hip.so``.
+input), ``include/qpsk_output.h`` (the same formats as output) and
+``include/qpsk_compact.h`` (the receive output as records of the valid frames),
+over ``singlecarrier_amd/libqpsk_hip.so``.
 
 There is no CPU fallback: if the HIP library is missing or no GPU is present,
 the receive functions raise.  (The CPU restatement in ``oracle/`` is test
@@ -191,6 +193,22 @@ def lib():
         L.qpsk_tx_batch_fmt.argtypes = [vp, vp, i32, vp, i32, C.c_long]
         L.qpsk_tx_batch_device_fmt.argtypes = [vp, vp, i32, vp, i32, C.c_long, vp]
         L.qpsk_tx_batch_device_fmt_path.argtypes = [vp, vp, i32, vp, i32, C.c_long, vp, i32]
+        sz, u32p = C.c_size_t, C.POINTER(C.c_uint32)
+        L.qpsk_bits_pack_host.argtypes = [vp, sz, vp]
+        L.qpsk_bits_unpack_host.argtypes = [vp, sz, vp]
+        L.qpsk_bits_pack_device.argtypes = [vp, sz, vp, vp]
+        L.qpsk_compact_host.argtypes = [vp, vp, vp, vp, i32, i32, i32, sz, vp, vp, vp, vp, vp]
+        L.qpsk_compact_work_bytes.restype = sz
+        L.qpsk_compact_work_bytes.argtypes = [i32, i32]
+        L.qpsk_compact_tiling.restype = None
+        L.qpsk_compact_tiling.argtypes = [C.POINTER(C.c_int)] * 3
+        L.qpsk_compact_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, sz, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.qpsk_rx_batch_records.argtypes = [vp, vp, i32, i32, sz, vp, vp, vp, vp, vp]
+        L.qpsk_rx_batch_records_fmt.argtypes = [vp, vp, i32, C.c_long, i32, i32, sz, vp, vp, vp, vp, vp]
+        L.qpsk_rx_batch_records_device.argtypes = [vp, vp, i32, i32, sz, vp, vp, vp, vp, vp, vp]
+        L.qpsk_stream_create_records.restype = vp
+        L.qpsk_stream_create_records.argtypes = [i32, i32, i32, i32, i32, i32, i32, sz, C.POINTER(C.c_int)]
+        L.qpsk_stream_retrieve_records.argtypes = [vp, C.POINTER(C.c_void_p), u32p, C.POINTER(C.c_void_p)]
         L.cnormf.restype = C.c_float
         L.cnormf.argtypes = [_CF]   # _Complex float == {float, float} in one SSE reg (SysV)
         _lib = L
@@ -217,7 +235,11 @@ SYMBOLS = ["qpsk_rx_create", "qpsk_rx_create_mode", "qpsk_rx_mode", "qpsk_rx_des
            "qpsk_rx_batch_fmt", "qpsk_rx_batch_device_fmt", "qpsk_stream_create_fmt",
            "qpsk_stream_acquire_raw",
            "qpsk_output_bytes", "qpsk_output_convert_host", "qpsk_output_convert_device",
-           "qpsk_tx_batch_fmt", "qpsk_tx_batch_device_fmt"]
+           "qpsk_tx_batch_fmt", "qpsk_tx_batch_device_fmt",
+           "qpsk_bits_pack_host", "qpsk_bits_unpack_host", "qpsk_bits_pack_device", "qpsk_compact_host",
+           "qpsk_compact_work_bytes", "qpsk_compact_tiling", "qpsk_compact_device", "qpsk_rx_batch_records",
+           "qpsk_rx_batch_records_fmt", "qpsk_rx_batch_records_device", "qpsk_stream_create_records",
+           "qpsk_stream_retrieve_records"]
 
 
 def _check(rc: int) -> None:
@@ -473,6 +495,149 @@ def _rx_tensors_check(nch: int, nf: int, bits, valid, trace, soft) -> None:
             raise ValueError(f"{name} must be a contiguous cuda tensor of shape {shape}")
 
 
+# --- the receive output as records (include/qpsk_compact.h) ---
+
+REC_BY_CHANNEL, REC_BY_FRAME = 0, 1
+# qpsk_frame_rec: 16 bytes, little endian
+REC_DTYPE = np.dtype([("channel", "<u4"), ("frame", "<u4"), ("bits", "<u8")])
+
+
+def compact_tiling() -> dict:
+    """qpsk_compact_tiling: the device compaction's tiling -- the items one
+    wave ranks (``run_items``), those of one workgroup (``block_items``) and
+    the counts the scan's workgroup takes per trip (``scan_trip``)."""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().qpsk_compact_tiling(C.byref(a), C.byref(b), C.byref(c))
+    return {"run_items": a.value, "block_items": b.value, "scan_trip": c.value}
+
+
+def compact_work_bytes(nch: int, nframes: int) -> int:
+    """qpsk_compact_work_bytes: bytes of compact_device's work area."""
+    return int(lib().qpsk_compact_work_bytes(nch, nframes))
+
+
+def pack_bits(bits) -> np.ndarray:
+    """qpsk_bits_pack_host: uint8 [..., 62] -> uint64 [...], bit i set iff
+    bits[..., i] == 1."""
+    bits = np.ascontiguousarray(bits, np.uint8)
+    if bits.ndim < 1 or bits.shape[-1] != NBITS:
+        raise ValueError(f"expected uint8 [...][{NBITS}], got {bits.shape}")
+    out = np.zeros(bits.shape[:-1], np.uint64)
+    _check(lib().qpsk_bits_pack_host(_ptr(bits), out.size, _ptr(out)))
+    return out
+
+
+def unpack_bits(words) -> np.ndarray:
+    """qpsk_bits_unpack_host: uint64 [...] -> uint8 [..., 62] of 0/1."""
+    words = np.ascontiguousarray(words, np.uint64)
+    out = np.zeros(words.shape + (NBITS,), np.uint8)
+    _check(lib().qpsk_bits_unpack_host(_ptr(words), words.size, _ptr(out)))
+    return out
+
+
+def pack_bits_device(bits, out=None, stream=None):
+    """qpsk_bits_pack_device: a contiguous cuda uint8 tensor [..., 62] -> an
+    int64 tensor [...] holding the words; enqueued on ``stream``."""
+    import torch
+    if not bits.is_cuda or bits.dtype != torch.uint8 or bits.shape[-1] != NBITS or not bits.is_contiguous():
+        raise ValueError(f"bits must be a contiguous cuda uint8 [...][{NBITS}] tensor")
+    if out is None:
+        out = torch.empty(tuple(bits.shape[:-1]), dtype=torch.int64, device=bits.device)
+    with torch.cuda.device(bits.device):
+        _check(lib().qpsk_bits_pack_device(bits.data_ptr(), out.numel(), out.data_ptr(),
+                                           _stream(stream, bits.device)))
+    return out
+
+
+def _groups_of(order: int, nch: int, nf: int) -> int:
+    return nf if order == REC_BY_FRAME else nch
+
+
+def _rec_arrays(cap: int, trace: bool, soft: bool, ngroups: int) -> dict:
+    """The host arrays a record call of at most cap records fills."""
+    o = {"rec": np.zeros(cap, REC_DTYPE), "groups": np.zeros(max(ngroups, 0) + 1, np.uint32)}
+    if trace:
+        o["trace"] = np.zeros((cap, 4), np.int32)
+    if soft:
+        o["soft"] = np.zeros((cap, DATA_SYMBOLS, 2), np.float32)
+    return o
+
+
+def _rec_trim(o: dict, count: int, cap: int) -> dict:
+    m = min(count, cap)
+    r = {k: (v if k == "groups" else v[:m]) for k, v in o.items()}
+    r["count"] = count
+    return r
+
+
+def compact_host(bits, valid, trace=None, soft=None, order: int = REC_BY_CHANNEL, cap: int | None = None,
+                 out: dict | None = None) -> dict:
+    """qpsk_compact_host: the dense outputs of a receive call (bits
+    [nch][nframes][62], valid [nch][nframes], optionally trace and soft) ->
+    {"rec" (REC_DTYPE), "count", "groups"} (+ "trace", "soft" rows), trimmed to
+    min(count, cap) rows; cap None = every frame.  ``out``: the arrays to write
+    into ("rec", "trace", "soft" of cap rows, "groups"; a missing one is not
+    made), returned untrimmed with "count"."""
+    valid = np.ascontiguousarray(valid, np.uint8)
+    if valid.ndim != 2:
+        raise ValueError(f"valid must be [nch][nframes], got {valid.shape}")
+    nch, nf = valid.shape
+    bits = np.ascontiguousarray(bits, np.uint8)
+    if bits.shape != (nch, nf, NBITS):
+        raise ValueError(f"bits must be [{nch}][{nf}][{NBITS}], got {bits.shape}")
+    if trace is not None:
+        trace = np.ascontiguousarray(trace, np.int32).reshape(nch, nf, 4)
+    if soft is not None:
+        soft = np.ascontiguousarray(soft, np.float32).reshape(nch, nf, DATA_SYMBOLS, 2)
+    cap = nch * nf if cap is None else int(cap)
+    o = out if out is not None else _rec_arrays(cap, trace is not None, soft is not None,
+                                                _groups_of(order, nch, nf))
+    count = C.c_uint32(0)
+    _check(lib().qpsk_compact_host(_ptr(bits), _ptr(valid), _ptr(trace), _ptr(soft), nch, nf, order, cap,
+                                   _ptr(o.get("rec")), _ptr(o.get("trace")), _ptr(o.get("soft")),
+                                   _ptr(o.get("groups")), C.addressof(count)))
+    return dict(o, count=int(count.value)) if out is not None else _rec_trim(o, int(count.value), cap)
+
+
+def compact_device(bits, valid, trace=None, soft=None, order: int = REC_BY_CHANNEL, cap: int | None = None,
+                   rec=None, rec_trace=None, rec_soft=None, groups=None, count=None, work=None, stream=None) -> dict:
+    """qpsk_compact_device on cuda tensors: bits uint8 [nch][nframes][62], valid
+    uint8 [nch][nframes] (+ trace int32 [..][4], soft float32 [..][31][2]).
+    Outputs (made when None): rec int64 [cap][2] (rec_from_tensor gives
+    REC_DTYPE on the host), rec_trace int32 [cap][4], rec_soft float32
+    [cap][31][2], groups and count int32 (holding the uint32 values), work
+    uint8 [compact_work_bytes].  Enqueued on ``stream``; returns the tensors
+    untrimmed."""
+    import torch
+    nch, nf = tuple(valid.shape)
+    dev = valid.device
+    cap = nch * nf if cap is None else int(cap)
+    if rec is None and cap > 0:
+        rec = torch.empty((cap, 2), dtype=torch.int64, device=dev)
+    if rec_trace is None and trace is not None:
+        rec_trace = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+    if rec_soft is None and soft is not None:
+        rec_soft = torch.empty((cap, DATA_SYMBOLS, 2), dtype=torch.float32, device=dev)
+    if groups is None:
+        groups = torch.empty(_groups_of(order, nch, nf) + 1, dtype=torch.int32, device=dev)
+    if count is None:
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+    if work is None:
+        work = torch.empty(compact_work_bytes(nch, nf), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().qpsk_compact_device(_ptr(bits), _ptr(valid), _ptr(trace), _ptr(soft), nch, nf, order, cap,
+                                         _ptr(rec), _ptr(rec_trace), _ptr(rec_soft), _ptr(groups), _ptr(count),
+                                         _ptr(work), work.numel(), _stream(stream, dev)))
+    return {"rec": rec, "trace": rec_trace, "soft": rec_soft, "groups": groups, "count": count, "work": work}
+
+
+def rec_from_tensor(rec, m: int | None = None) -> np.ndarray:
+    """A device record tensor (int64 [cap][2]) as a REC_DTYPE array on the host
+    (its first m rows)."""
+    a = rec.cpu().numpy() if m is None else rec[:m].cpu().numpy()
+    return np.ascontiguousarray(a).view(REC_DTYPE).reshape(-1)
+
+
 class Receiver:
     """A batch of ``nch`` independent receivers on one GPU (``qpsk_ctx``).
 
@@ -598,6 +763,59 @@ class Receiver:
         _rx_tensors_check(self.nch, nf, bits, valid, trace, soft)
         _check(lib().qpsk_rx_batch_device_fmt(self._h, x.data_ptr(), fmt, ld, nf, _ptr(bits), _ptr(valid),
                                               _ptr(trace), _ptr(soft), _stream(stream, x.device)))
+
+    def demod_records(self, x, order: int = REC_BY_CHANNEL, cap: int | None = None, trace: bool = False,
+                      soft: bool = False) -> dict:
+        """``demod`` whose output is the list of the valid frames
+        (qpsk_rx_batch_records): {"rec" (REC_DTYPE: channel, frame, bits),
+        "count", "groups"} (+ "trace", "soft" rows), in ``order``, trimmed to
+        min(count, cap) rows.  The dense outputs never leave the device."""
+        x = np.ascontiguousarray(x, dtype=np.int16)
+        if x.ndim != 3 or x.shape[0] != self.nch or x.shape[2] != FRAME_SIZE:
+            raise ValueError(f"expected int16 [{self.nch}][nframes][{FRAME_SIZE}], got {x.shape}")
+        nf = x.shape[1]
+        cap = self.nch * nf if cap is None else int(cap)
+        o = _rec_arrays(cap, trace, soft, _groups_of(order, self.nch, nf))
+        count = C.c_uint32(0)
+        _check(lib().qpsk_rx_batch_records(self._h, _ptr(x), nf, order, cap, _ptr(o["rec"]), _ptr(o.get("trace")),
+                                           _ptr(o.get("soft")), _ptr(o["groups"]), C.addressof(count)))
+        return _rec_trim(o, int(count.value), cap)
+
+    def demod_records_fmt(self, x, fmt: int, order: int = REC_BY_CHANNEL, cap: int | None = None,
+                          trace: bool = False, soft: bool = False) -> dict:
+        """``demod_records`` for a host source block in format ``fmt`` (as
+        demod_fmt takes it; qpsk_rx_batch_records_fmt)."""
+        _fmt_check(fmt, self.nch)
+        x, nf, ld = _np_block(x, fmt, self.nch)
+        cap = self.nch * nf if cap is None else int(cap)
+        o = _rec_arrays(cap, trace, soft, _groups_of(order, self.nch, nf))
+        count = C.c_uint32(0)
+        _check(lib().qpsk_rx_batch_records_fmt(self._h, _ptr(x), fmt, ld, nf, order, cap, _ptr(o["rec"]),
+                                               _ptr(o.get("trace")), _ptr(o.get("soft")), _ptr(o["groups"]),
+                                               C.addressof(count)))
+        return _rec_trim(o, int(count.value), cap)
+
+    def demod_records_device(self, x, order: int = REC_BY_CHANNEL, cap: int | None = None, trace: bool = False,
+                             soft: bool = False, stream=None) -> dict:
+        """``demod_device`` whose output is records, all on the device and
+        asynchronous on ``stream`` (qpsk_rx_batch_records_device): returns the
+        tensors of compact_device, untrimmed; check with ``sync``."""
+        import torch
+        if x.dtype != torch.int16 or x.dim() != 3 or x.shape[0] != self.nch \
+                or x.shape[2] != FRAME_SIZE or not x.is_contiguous() or not x.is_cuda:
+            raise ValueError("x must be a contiguous cuda int16 [nch][nframes][1880] tensor")
+        nf = x.shape[1]
+        cap = self.nch * nf if cap is None else int(cap)
+        dev = x.device
+        with torch.cuda.device(dev), torch.cuda.stream(stream or torch.cuda.current_stream(dev)):
+            rec = torch.empty((cap, 2), dtype=torch.int64, device=dev) if cap > 0 else None
+            rtr = torch.empty((cap, 4), dtype=torch.int32, device=dev) if trace else None
+            rso = torch.empty((cap, DATA_SYMBOLS, 2), dtype=torch.float32, device=dev) if soft else None
+            groups = torch.empty(_groups_of(order, self.nch, nf) + 1, dtype=torch.int32, device=dev)
+            count = torch.empty(1, dtype=torch.int32, device=dev)
+            _check(lib().qpsk_rx_batch_records_device(self._h, _ptr(x), nf, order, cap, _ptr(rec), _ptr(rtr),
+                                                      _ptr(rso), _ptr(groups), _ptr(count), _stream(stream, dev)))
+        return {"rec": rec, "trace": rtr, "soft": rso, "groups": groups, "count": count}
 
     def sync(self) -> None:
         """Wait for the latest demod_device call; raise QpskError (QPSK_ESTALL)
@@ -759,12 +977,20 @@ class Stream:
     ``acquire()`` in place, ``submit()``, later ``retrieve()`` the oldest chunk.
     Every channel's state carries across chunks.  With ``fmt`` other than
     planar int16 (IN_*) the chunks are source blocks in that format, filled
-    through ``acquire_raw()`` and converted on the GPU."""
+    through ``acquire_raw()`` and converted on the GPU.  With ``records=True``
+    the chunks come back through ``retrieve_records()`` as the list of their
+    valid frames in ``order``, at most ``cap`` a chunk (include/qpsk_compact.h)."""
 
     def __init__(self, nch: int, frames: int, nslot: int = 3, device: int = 0,
-                 mode: int = MODE_REFERENCE, fmt: int = IN_S16 | IN_PLANAR):
+                 mode: int = MODE_REFERENCE, fmt: int = IN_S16 | IN_PLANAR, records: bool = False,
+                 order: int = REC_BY_CHANNEL, cap: int | None = None):
         err = C.c_int(0)
-        if fmt == IN_S16 | IN_PLANAR:
+        self.records, self.order = bool(records), order
+        self.cap = min(nch * frames, nch * frames if cap is None else int(cap))
+        if records:
+            self._h = lib().qpsk_stream_create_records(device, nch, frames, nslot, mode, fmt, order, self.cap,
+                                                       C.byref(err))
+        elif fmt == IN_S16 | IN_PLANAR:
             self._h = lib().qpsk_stream_create_mode(device, nch, frames, nslot, mode, C.byref(err))
         else:
             self._h = lib().qpsk_stream_create_fmt(device, nch, frames, nslot, mode, fmt, C.byref(err))
@@ -821,6 +1047,18 @@ class Stream:
         bits = bits.reshape(self.nch, self.frames, NBITS)
         valid = valid.reshape(self.nch, self.frames)
         return (bits.copy(), valid.copy()) if copy else (bits, valid)
+
+    def retrieve_records(self, copy: bool = True) -> dict:
+        """{"rec" (REC_DTYPE, min(count, cap) of them), "count", "groups"} of
+        the oldest chunk of a ``records=True`` stream."""
+        r, g, count = C.c_void_p(), C.c_void_p(), C.c_uint32(0)
+        _check(lib().qpsk_stream_retrieve_records(self._h, C.byref(r), C.byref(count), C.byref(g)))
+        m = min(int(count.value), self.cap)
+        ng = _groups_of(self.order, self.nch, self.frames) + 1
+        rec = np.frombuffer((C.c_uint8 * (16 * m)).from_address(r.value), REC_DTYPE) if m else np.zeros(0, REC_DTYPE)
+        groups = np.frombuffer((C.c_uint32 * ng).from_address(g.value), np.uint32)
+        return {"rec": rec.copy() if copy else rec, "count": int(count.value),
+                "groups": groups.copy() if copy else groups}
 
 
 def cnormf(val: complex) -> float:

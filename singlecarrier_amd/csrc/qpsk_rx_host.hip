@@ -212,6 +212,16 @@ struct FmtInput {
     qhip::DevBuf<int16_t> conv;
 };
 
+// a record call's buffers (include/qpsk_compact.h, built in qpsk_compact.hip on
+// qpsk_rx_rec_bufs): the dense outputs that stay on the device, the
+// compaction's work area and a host call's result block.  Empty until such a call.
+struct RecBufs {
+    qhip::DevBuf<uint8_t> bits, valid;
+    qhip::DevBuf<int32_t> trace;
+    qhip::DevBuf<float> soft;
+    qhip::DevBuf<char> work, out;
+};
+
 // kernel-span accounting: events before rx_kernel, between the kernels, after
 // rx_data_kernel, from a pool that is folded into running sums when it is full
 struct SpanTimer {
@@ -289,6 +299,7 @@ struct qpsk_ctx {
     JobQueue q;
     Staging stage;
     FmtInput fmt;
+    RecBufs rec;
     SpanTimer spans;
     RxKnobs knobs;
     Assembly assembly;
@@ -882,6 +893,27 @@ int qpsk_rx_fmt_conv(qpsk_ctx* c, size_t n, int16_t** p) {
     *p = c->fmt.conv;
     return QPSK_OK;
 }
+
+int qpsk_rx_rec_bufs(qpsk_ctx* c, size_t cf, bool trace, bool soft, size_t work_bytes, size_t out_bytes,
+                     qpsk_rec_bufs* b) {
+    if (!c || !b) return QPSK_EINVAL;
+    HCHECK(hipSetDevice(c->device));
+    RecBufs& r = c->rec;
+    const size_t ntr = trace ? cf * 4 : 0, nso = soft ? cf * QK_NDSYM * 2 : 0;
+    if (cf * QK_NBITS > r.bits.cap() || cf > r.valid.cap() || ntr > r.trace.cap() || nso > r.soft.cap() ||
+        work_bytes > r.work.cap() || out_bytes > r.out.cap())
+        HCHECK(hipDeviceSynchronize());   // an earlier call may still use the buffers
+    HCHECK(r.bits.reserve(cf * QK_NBITS));
+    HCHECK(r.valid.reserve(cf));
+    HCHECK(r.trace.reserve(ntr));
+    HCHECK(r.soft.reserve(nso));
+    HCHECK(r.work.reserve(work_bytes));
+    HCHECK(r.out.reserve(out_bytes));
+    *b = qpsk_rec_bufs{r.bits, r.valid, trace ? r.trace.get() : nullptr, soft ? r.soft.get() : nullptr, r.work, r.out};
+    return QPSK_OK;
+}
+
+hipStream_t qpsk_rx_stream(qpsk_ctx* c) { return c ? (hipStream_t)c->stream : nullptr; }
 
 extern "C" const char* qpsk_strerror(int err) {
     switch (err) {

@@ -52,6 +52,50 @@ struct qpsk_stream;
 qpsk_stream* qpsk_stream_create_raw(int device, int nch, int frames, int nslot, int mode, int fmt,
                                     size_t raw_bytes, qpsk_convert_fn convert, int* err);
 
+// Records in place of the dense outputs (include/qpsk_compact.h).  As with the
+// input formats, the receive path and the streams know nothing of records:
+// qpsk_compact.hip, which has the compaction, builds the record entry points on
+// the hooks below, and neither qpsk_rx_host.hip nor qpsk_stream.hip refers to
+// a symbol of it.
+//
+// Grow-only device buffers of the context for a record call of cf
+// channel-frames: the dense intermediates (trace / soft only when asked for),
+// the compaction's work area, and for host calls the block the results are
+// made in before they are copied back (out_bytes, 0 for none; 16-byte
+// aligned).  A call larger than every earlier one waits for the device before
+// a buffer is reallocated.
+struct qpsk_rec_bufs {
+    uint8_t *bits, *valid;
+    int32_t* trace;
+    float* soft;
+    void* work;
+    char* out;
+};
+int qpsk_rx_rec_bufs(qpsk_ctx* c, size_t cf, bool trace, bool soft, size_t work_bytes, size_t out_bytes,
+                     qpsk_rec_bufs* b);
+// the context's own stream (what its host calls run on)
+hipStream_t qpsk_rx_stream(qpsk_ctx* c);
+// A stream whose chunks come back through a post-receive pass: submit runs
+// `compact` on the receive stream behind the receive, on the slot's dense
+// bits / valid, and copies back the count and the groups (uint32 [1 + ngroups
+// + 1] in one block) instead of the dense arrays; qpsk_stream_retrieve_post
+// then copies min(count, cap) records of rec_bytes each.
+struct qpsk_stream_post {
+    int order = 0;
+    size_t cap = 0, rec_bytes = 0, ngroups = 0, work_bytes = 0;
+    int (*compact)(const uint8_t* d_bits, const uint8_t* d_valid, int nch, int nframes, int order, size_t cap,
+                   void* d_rec, uint32_t* d_groups, uint32_t* d_count, void* d_work, size_t work_bytes,
+                   void* stream) = nullptr;
+};
+struct qpsk_stream;
+// qpsk_stream_create_raw (convert may be nullptr: planar int16 chunks) with a
+// post-receive pass (post == nullptr: none)
+qpsk_stream* qpsk_stream_create_post(int device, int nch, int frames, int nslot, int mode, int fmt,
+                                     size_t raw_bytes, qpsk_convert_fn convert, const qpsk_stream_post* post,
+                                     int* err);
+// qpsk_stream_retrieve for such a stream (QPSK_EINVAL on any other)
+int qpsk_stream_retrieve_post(qpsk_stream* s, const void** rec, uint32_t* count, const uint32_t** groups);
+
 // The stream that owns a context (qpsk_stream_create_mode): qpsk_rx_reset()
 // and qpsk_rx_state_load() refuse with QPSK_EBUSY while it has chunks pending.
 struct qpsk_stream;

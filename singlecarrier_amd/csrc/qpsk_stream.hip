@@ -29,6 +29,13 @@ struct Slot {
     qhip::PinBuf<uint8_t> h_bits, h_valid;
     qhip::DevBuf<int> d_err;     // the chunk's device error word (progress-wait stalls)
     qhip::PinBuf<int> h_err;     // pinned copy, read by qpsk_stream_retrieve
+    // a stream with a post-receive pass (qpsk_stream_create_post): the records
+    // on the device and pinned, and the count with the groups (one block) in
+    // place of h_bits / h_valid
+    qhip::DevBuf<char> d_rec;
+    qhip::PinBuf<char> h_rec;
+    qhip::DevBuf<uint32_t> d_hdr;
+    qhip::PinBuf<uint32_t> h_hdr;
     qhip::Event copied, received, done;
     uint64_t epoch = 0;          // qpsk_rx_epoch() when the chunk was submitted
 };
@@ -48,12 +55,17 @@ struct qpsk_stream {
     size_t raw_bytes = 0;
     qpsk_convert_fn convert = nullptr;
     bool plain() const { return convert == nullptr; }
+    // chunks that come back through a post-receive pass (qpsk_stream_create_post)
+    bool has_post = false;
+    qpsk_stream_post post;
+    qhip::DevBuf<char> work;   // the pass's work area: one, the passes run in order on s_rx
     // released in reverse order: the slots, the streams, then the receiver
     struct RxDestroy {
         void operator()(qpsk_ctx* c) const { qpsk_rx_destroy(c); }
     };
     std::unique_ptr<qpsk_ctx, RxDestroy> rx;
     qhip::Stream s_h2d, s_rx, s_d2h;
+    qhip::Stream s_rec;   // a post stream's copy of a retrieved chunk's records
     Slot slot[kMaxSlots];
     uint64_t acquired = 0, submitted = 0, retrieved = 0;
     // A stalled chunk leaves every channel's carried state (rx_timing, windows,
@@ -70,6 +82,10 @@ static int stream_alloc(qpsk_stream* s) {
     HCHECK(s->s_h2d.create());
     HCHECK(s->s_rx.create());
     HCHECK(s->s_d2h.create());
+    if (s->has_post) {
+        HCHECK(s->s_rec.create());
+        HCHECK(s->work.reserve(s->post.work_bytes));
+    }
     const size_t cf = (size_t)s->nch * (size_t)s->frames;
     for (int i = 0; i < s->nslot; i++) {
         Slot& q = s->slot[i];
@@ -79,8 +95,15 @@ static int stream_alloc(qpsk_stream* s) {
             HCHECK(q.h_raw.reserve(s->raw_bytes));
             HCHECK(q.d_raw.reserve(s->raw_bytes));
         }
-        HCHECK(q.h_bits.reserve(cf * QK_NBITS));
-        HCHECK(q.h_valid.reserve(cf));
+        if (s->has_post) {
+            HCHECK(q.h_rec.reserve(s->post.cap * s->post.rec_bytes));
+            HCHECK(q.d_rec.reserve(s->post.cap * s->post.rec_bytes));
+            HCHECK(q.d_hdr.reserve(s->post.ngroups + 2));
+            HCHECK(q.h_hdr.reserve(s->post.ngroups + 2));
+        } else {
+            HCHECK(q.h_bits.reserve(cf * QK_NBITS));
+            HCHECK(q.h_valid.reserve(cf));
+        }
         HCHECK(q.d_in.reserve(cf * QK_FRAME));
         HCHECK(q.d_bits.reserve(cf * QK_NBITS));
         HCHECK(q.d_valid.reserve(cf));
@@ -104,8 +127,15 @@ extern "C" qpsk_stream* qpsk_stream_create_mode(int device, int nch, int frames,
 
 qpsk_stream* qpsk_stream_create_raw(int device, int nch, int frames, int nslot, int mode, int fmt,
                                     size_t raw_bytes, qpsk_convert_fn convert, int* err) {
+    return qpsk_stream_create_post(device, nch, frames, nslot, mode, fmt, raw_bytes, convert, nullptr, err);
+}
+
+qpsk_stream* qpsk_stream_create_post(int device, int nch, int frames, int nslot, int mode, int fmt,
+                                     size_t raw_bytes, qpsk_convert_fn convert, const qpsk_stream_post* post,
+                                     int* err) {
     if (nch < 1 || frames < 1 || nslot < 1 || nslot > kMaxSlots) return qhip::fail(err, QPSK_EINVAL);
     if (convert && raw_bytes == 0) return qhip::fail(err, QPSK_EINVAL);
+    if (post && (!post->compact || post->rec_bytes == 0)) return qhip::fail(err, QPSK_EINVAL);
     qpsk_stream* s = new (std::nothrow) qpsk_stream();
     if (!s) return qhip::fail(err, QPSK_ENOMEM);
     s->device = device;
@@ -115,6 +145,10 @@ qpsk_stream* qpsk_stream_create_raw(int device, int nch, int frames, int nslot, 
     s->fmt = fmt;
     s->raw_bytes = raw_bytes;
     s->convert = convert;
+    if (post) {
+        s->has_post = true;
+        s->post = *post;
+    }
     int r = QPSK_OK;
     s->rx.reset(qpsk_rx_create_mode(device, nch, mode, &r));
     if (s->rx) {
@@ -135,6 +169,7 @@ extern "C" void qpsk_stream_destroy(qpsk_stream* s) {
     (void)hipStreamSynchronize(s->s_h2d);
     (void)hipStreamSynchronize(s->s_rx);
     (void)hipStreamSynchronize(s->s_d2h);
+    if (s->has_post) (void)hipStreamSynchronize(s->s_rec);
     delete s;
 }
 
@@ -186,10 +221,21 @@ extern "C" int qpsk_stream_submit(qpsk_stream* s) {
     if (r != QPSK_OK) return r;
     hipLaunchKernelGGL(err_merge_kernel, dim3(1), dim3(64), 0, s->s_rx, qpsk_rx_err_word(s->rx.get()), q.d_err);
     HCHECK(hipGetLastError());
+    if (s->has_post) {   // the dense outputs -> records, count and groups, behind the receive
+        const qpsk_stream_post& p = s->post;
+        const int pr = p.compact(q.d_bits, q.d_valid, s->nch, s->frames, p.order, p.cap,
+                                 q.d_rec, q.d_hdr + 1, q.d_hdr, s->work, p.work_bytes, s->s_rx);
+        if (pr != QPSK_OK) return pr;
+    }
     HCHECK(hipEventRecord(q.received, s->s_rx));
     HCHECK(hipStreamWaitEvent(s->s_d2h, q.received, 0));
-    HCHECK(hipMemcpyAsync(q.h_bits, q.d_bits, cf * QK_NBITS, hipMemcpyDeviceToHost, s->s_d2h));
-    HCHECK(hipMemcpyAsync(q.h_valid, q.d_valid, cf, hipMemcpyDeviceToHost, s->s_d2h));
+    if (s->has_post) {
+        HCHECK(hipMemcpyAsync(q.h_hdr, q.d_hdr, sizeof(uint32_t) * (s->post.ngroups + 2), hipMemcpyDeviceToHost,
+                              s->s_d2h));
+    } else {
+        HCHECK(hipMemcpyAsync(q.h_bits, q.d_bits, cf * QK_NBITS, hipMemcpyDeviceToHost, s->s_d2h));
+        HCHECK(hipMemcpyAsync(q.h_valid, q.d_valid, cf, hipMemcpyDeviceToHost, s->s_d2h));
+    }
     HCHECK(hipMemcpyAsync(q.h_err, q.d_err, sizeof(int), hipMemcpyDeviceToHost, s->s_d2h));
     HCHECK(hipEventRecord(q.done, s->s_d2h));
     q.epoch = qpsk_rx_epoch(s->rx.get());
@@ -201,13 +247,8 @@ extern "C" int qpsk_stream_pending(const qpsk_stream* s) {
     return s ? (int)(s->submitted - s->retrieved) : 0;
 }
 
-extern "C" int qpsk_stream_retrieve(qpsk_stream* s, const uint8_t** bits, const uint8_t** valid) {
-    if (!s || !bits || !valid || s->retrieved == s->submitted) return QPSK_EINVAL;
-    Slot& q = s->slot[s->retrieved % (uint64_t)s->nslot];
-    HCHECK(hipSetDevice(s->device));
-    HCHECK(hipEventSynchronize(q.done));
-    *bits = q.h_bits;
-    *valid = q.h_valid;
+// the verdict of the chunk in slot q, which has just been retrieved
+static int retrieved_verdict(qpsk_stream* s, Slot& q) {
     s->retrieved++;
     // a progress wait of this chunk's receive ran out: its bits are undefined,
     // and so are those of every later chunk of its epoch, which start from the
@@ -220,6 +261,33 @@ extern "C" int qpsk_stream_retrieve(qpsk_stream* s, const uint8_t** bits, const 
         qpsk_rx_mark_stalled(s->rx.get(), q.epoch);   // the context's state too (qpsk_rx_state_save)
     }
     return (s->stalled && q.epoch == s->stall_epoch) ? QPSK_ESTALL : QPSK_OK;
+}
+
+extern "C" int qpsk_stream_retrieve(qpsk_stream* s, const uint8_t** bits, const uint8_t** valid) {
+    if (!s || s->has_post || !bits || !valid || s->retrieved == s->submitted) return QPSK_EINVAL;
+    Slot& q = s->slot[s->retrieved % (uint64_t)s->nslot];
+    HCHECK(hipSetDevice(s->device));
+    HCHECK(hipEventSynchronize(q.done));
+    *bits = q.h_bits;
+    *valid = q.h_valid;
+    return retrieved_verdict(s, q);
+}
+
+int qpsk_stream_retrieve_post(qpsk_stream* s, const void** rec, uint32_t* count, const uint32_t** groups) {
+    if (!s || !s->has_post || !rec || !count || !groups || s->retrieved == s->submitted) return QPSK_EINVAL;
+    Slot& q = s->slot[s->retrieved % (uint64_t)s->nslot];
+    HCHECK(hipSetDevice(s->device));
+    HCHECK(hipEventSynchronize(q.done));
+    *count = q.h_hdr[0];
+    *groups = q.h_hdr + 1;
+    *rec = q.h_rec;
+    // the count is known: that many records, at most cap, and nothing else
+    const size_t m = *count < s->post.cap ? (size_t)*count : s->post.cap;
+    if (m > 0) {
+        HCHECK(hipMemcpyAsync(q.h_rec, q.d_rec, m * s->post.rec_bytes, hipMemcpyDeviceToHost, s->s_rec));
+        HCHECK(hipStreamSynchronize(s->s_rec));
+    }
+    return retrieved_verdict(s, q);
 }
 
 extern "C" qpsk_ctx* qpsk_stream_ctx(qpsk_stream* s) { return s ? s->rx.get() : nullptr; }

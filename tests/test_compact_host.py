@@ -1,0 +1,230 @@
+"""The host twin of the record layer (include/qpsk_compact.h,
+csrc/qpsk_compact_host.c) against a numpy restatement written from the header
+comment alone: np.argwhere(valid) is the by-channel order, np.argwhere(valid.T)
+the by-frame order, and a record's word is sum((bits[i] == 1) << i).  No GPU."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import singlecarrier_amd as sc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "singlecarrier_amd", "csrc")
+INC = os.path.join(ROOT, "include")
+SENT = 0xA5   # the fill of every output array before a call
+
+
+def restate(bits, valid, trace, soft, order):
+    """(channel, frame, words, trace rows, soft rows, groups) of the whole list."""
+    nch, nf = valid.shape
+    if order == sc.REC_BY_FRAME:
+        fc = np.argwhere(valid.T != 0)
+        f, c = fc[:, 0], fc[:, 1]
+        per = (valid != 0).sum(axis=0)
+    else:
+        cf = np.argwhere(valid != 0)
+        c, f = cf[:, 0], cf[:, 1]
+        per = (valid != 0).sum(axis=1)
+    w = ((bits[c, f] == 1).astype(np.uint64) << np.arange(62, dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
+    groups = np.concatenate([[0], np.cumsum(per)]).astype(np.uint32)
+    return c, f, w, trace[c, f], soft[c, f], groups
+
+
+def dense(rng, nch, nf, density, odd_bytes=False):
+    valid = (rng.random((nch, nf)) < density).astype(np.uint8)
+    valid *= rng.integers(1, 4, (nch, nf), dtype=np.uint8)   # any nonzero flag is valid
+    bits = rng.integers(0, 2, (nch, nf, 62), dtype=np.uint8)
+    if odd_bytes:
+        bits[rng.random(bits.shape) < 0.2] = 2
+        bits[rng.random(bits.shape) < 0.2] = 255
+    trace = rng.integers(-2**31, 2**31 - 1, (nch, nf, 4)).astype(np.int32)
+    soft = rng.standard_normal((nch, nf, 31, 2)).astype(np.float32)
+    return bits, valid, trace, soft
+
+
+def filled(cap, ngroups):
+    o = {"rec": np.zeros(cap, sc.REC_DTYPE), "trace": np.zeros((cap, 4), np.int32),
+         "soft": np.zeros((cap, 31, 2), np.float32), "groups": np.zeros(ngroups + 1, np.uint32)}
+    for a in o.values():
+        a.view(np.uint8)[...] = SENT
+    return o
+
+
+def check(bits, valid, trace, soft, order, cap):
+    nch, nf = valid.shape
+    c, f, w, tr, so, groups = restate(bits, valid, trace, soft, order)
+    count = len(c)
+    G = nf if order == sc.REC_BY_FRAME else nch
+    o = sc.compact_host(bits, valid, trace, soft, order=order, cap=cap, out=filled(cap, G))
+    m = min(count, cap)
+    assert o["count"] == count == int((valid != 0).sum())
+    np.testing.assert_array_equal(o["groups"], groups)
+    assert o["groups"][G] == count
+    np.testing.assert_array_equal(o["rec"]["channel"][:m], c[:m])
+    np.testing.assert_array_equal(o["rec"]["frame"][:m], f[:m])
+    np.testing.assert_array_equal(o["rec"]["bits"][:m], w[:m])
+    assert (o["rec"]["bits"][:m] >> np.uint64(62) == 0).all()
+    np.testing.assert_array_equal(o["trace"][:m], tr[:m])
+    np.testing.assert_array_equal(o["soft"][:m].view(np.uint32), so[:m].view(np.uint32))
+    for k in ("rec", "trace", "soft"):   # nothing past min(count, cap) rows
+        assert (o[k][m:].view(np.uint8) == SENT).all(), k
+    return count
+
+
+@pytest.mark.parametrize("order", [sc.REC_BY_CHANNEL, sc.REC_BY_FRAME])
+@pytest.mark.parametrize("nch,nf", [(1, 1), (1, 17), (17, 1), (5, 7), (64, 9), (130, 33)])
+@pytest.mark.parametrize("density", [0.0, 1.0, 0.2])
+def test_against_numpy(nch, nf, density, order):
+    rng = np.random.default_rng(nch * 1000 + nf)
+    d = dense(rng, nch, nf, density, odd_bytes=True)
+    count = check(*d, order, nch * nf)
+    for cap in (0, count - 1, count, count + 5):
+        if cap >= 0:
+            check(*d, order, cap)
+
+
+@pytest.mark.parametrize("order", [sc.REC_BY_CHANNEL, sc.REC_BY_FRAME])
+def test_empty_leading_middle_and_trailing_groups(order):
+    rng = np.random.default_rng(5)
+    bits, valid, trace, soft = dense(rng, 9, 9, 0.6)
+    for k in (0, 1, 4, 5, 8):   # channels and frames with nothing valid
+        valid[k, :] = 0
+        valid[:, k] = 0
+    assert valid.any()
+    check(bits, valid, trace, soft, order, 81)
+    o = sc.compact_host(bits, valid, order=order)
+    g = o["groups"]
+    for k in (0, 1, 4, 5, 8):
+        assert g[k] == g[k + 1]
+    assert g[0] == 0 and g[9] == o["count"] == len(o["rec"])
+
+
+def test_bytes_other_than_one_pack_as_zero():
+    bits = np.zeros((4, 62), np.uint8)
+    bits[0, :] = 2
+    bits[1, :] = 255
+    bits[2, ::2] = 1
+    bits[2, 1::2] = 254
+    bits[3, :] = 1
+    w = sc.pack_bits(bits)
+    assert w[0] == 0 and w[1] == 0
+    assert w[2] == sum(1 << i for i in range(0, 62, 2))
+    assert w[3] == (1 << 62) - 1
+    o = sc.compact_host(bits[None], np.ones((1, 4), np.uint8))
+    np.testing.assert_array_equal(o["rec"]["bits"], w)
+
+
+def test_bit_order_is_the_transmitters():
+    """bit 2s = Q = bits[2s], bit 2s+1 = I = bits[2s+1] (qpsk_tx.h)."""
+    bits = np.zeros((1, 62), np.uint8)
+    bits[0, 2 * 5] = 1       # Q of symbol 5
+    bits[0, 2 * 30 + 1] = 1  # I of symbol 30
+    assert int(sc.pack_bits(bits)[0]) == (1 << 10) | (1 << 61)
+
+
+def test_pack_unpack_round_trip():
+    rng = np.random.default_rng(2)
+    bits = rng.integers(0, 2, (7, 11, 62), dtype=np.uint8)
+    w = sc.pack_bits(bits)
+    assert w.shape == (7, 11) and w.dtype == np.uint64
+    np.testing.assert_array_equal(sc.unpack_bits(w), bits)
+    np.testing.assert_array_equal(sc.pack_bits(np.zeros((3, 62), np.uint8)), np.zeros(3, np.uint64))
+    assert sc.pack_bits(np.zeros((0, 62), np.uint8)).shape == (0,)
+
+
+def test_pure_count_and_optional_outputs():
+    rng = np.random.default_rng(3)
+    bits, valid, trace, soft = dense(rng, 6, 5, 0.5)
+    L = sc.lib()
+    count = C.c_uint32(0)
+    assert L.qpsk_compact_host(bits.ctypes.data, valid.ctypes.data, None, None, 6, 5, 0, 0, None, None, None, None,
+                               C.addressof(count)) == 0
+    assert count.value == (valid != 0).sum()
+    # a gathered array without its dense source is left alone
+    o = filled(30, 6)
+    del o["soft"]
+    r = sc.compact_host(bits, valid, None, None, cap=30, out=o)
+    assert (r["trace"].view(np.uint8) == SENT).all()
+
+
+def test_every_einval():
+    L = sc.lib()
+    bits = np.zeros((2, 3, 62), np.uint8)
+    valid = np.ones((2, 3), np.uint8)
+    rec = np.zeros(6, sc.REC_DTYPE)
+    count = C.c_uint32(99)
+    b, v, r, n = bits.ctypes.data, valid.ctypes.data, rec.ctypes.data, C.addressof(count)
+
+    def call(bits=b, valid=v, nch=2, nf=3, order=0, cap=6, rec=r, count=n):
+        return L.qpsk_compact_host(bits, valid, None, None, nch, nf, order, cap, rec, None, None, None, count)
+
+    assert call() == 0 and count.value == 6
+    count.value = 99
+    for kw in (dict(order=2), dict(order=-1), dict(nch=-1), dict(nf=-1), dict(nch=1 << 14, nf=1 << 14),
+               dict(bits=None), dict(valid=None), dict(count=None), dict(rec=None), dict(rec=None, cap=1)):
+        assert call(**kw) == sc.QPSK_EINVAL, kw
+    assert count.value == 99
+    assert call(nch=(1 << 28) - 1, nf=1, cap=0, rec=None, valid=None) == sc.QPSK_EINVAL   # NULL valid, not the size
+    assert call(rec=None, cap=0) == 0   # a pure count
+    assert call(nch=0, bits=None, valid=None) == 0 and count.value == 0   # no items: nothing to read
+    # the device call's checks come before any HIP call: no GPU is touched
+    work = 1 << 20
+    assert L.qpsk_compact_device(b, v, None, None, 2, 3, 5, 6, r, None, None, None, n, r, work, None) == sc.QPSK_EINVAL
+    assert L.qpsk_compact_device(b, v, None, None, 2, -3, 0, 6, r, None, None, None, n, r, work, None) == sc.QPSK_EINVAL
+    assert L.qpsk_compact_device(b, v, None, None, 2, 3, 0, 6, None, None, None, None, n, r, work, None) == sc.QPSK_EINVAL
+    assert L.qpsk_compact_device(b, v, None, None, 2, 3, 0, 6, r, None, None, None, None, r, work, None) == sc.QPSK_EINVAL
+    assert L.qpsk_compact_device(None, v, None, None, 2, 3, 0, 6, r, None, None, None, n, r, work, None) == sc.QPSK_EINVAL
+    assert L.qpsk_compact_device(b, v, None, None, 2, 3, 0, 6, r, None, None, None, n, None, work, None) == sc.QPSK_EINVAL
+    assert L.qpsk_compact_device(b, v, None, None, 2, 3, 0, 6, r, None, None, None, n, r, 3, None) == sc.QPSK_EINVAL
+    assert L.qpsk_compact_device(b, v, None, None, 1 << 14, 1 << 14, 0, 6, r, None, None, None, n, r, work,
+                                 None) == sc.QPSK_EINVAL
+    # record calls on no context, and an unknown order on a stream
+    assert L.qpsk_rx_batch_records(None, b, 1, 0, 0, None, None, None, None, n) == sc.QPSK_EINVAL
+    assert L.qpsk_rx_batch_records_device(None, b, 1, 0, 0, None, None, None, None, n, None) == sc.QPSK_EINVAL
+    err = C.c_int(0)
+    assert not L.qpsk_stream_create_records(0, 4, 2, 3, 0, 0, 7, 8, C.byref(err)) and err.value == sc.QPSK_EINVAL
+    assert L.qpsk_stream_retrieve_records(None, None, None, None) == sc.QPSK_EINVAL
+
+
+def test_work_bytes_and_tiling():
+    t = sc.compact_tiling()
+    assert t["run_items"] % 64 == 0 and t["block_items"] % t["run_items"] == 0 and t["scan_trip"] % 64 == 0
+    run = t["run_items"]
+    assert sc.compact_work_bytes(1, 1) == 4
+    assert sc.compact_work_bytes(1, run) == 4 and sc.compact_work_bytes(1, run + 1) == 8
+    assert sc.compact_work_bytes(65536, 32) == 4 * (65536 * 32 // run)
+    assert sc.compact_work_bytes(-1, 1) == 0 and sc.compact_work_bytes(1 << 14, 1 << 14) == 0
+    assert sc.REC_DTYPE.itemsize == 16
+
+
+def test_sanitized_host_twin(tmp_path):
+    """csrc/qpsk_compact_host.c and tests/sanitize/compact_check.c (its own
+    main, every array a heap block of exactly the stated size) under ASan +
+    UBSan on the CPU: any report aborts the run."""
+    if shutil.which("gcc") is None:
+        pytest.skip("gcc not available")
+    exe = str(tmp_path / "compact_check")
+    subprocess.run(["gcc", "-std=gnu11", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I" + INC, "-I" + CSRC, "-o", exe,
+                    os.path.join(ROOT, "tests", "sanitize", "compact_check.c"),
+                    os.path.join(CSRC, "qpsk_compact_host.c")], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "0 failures" in r.stdout
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+
+
+@pytest.mark.parametrize("cc,std", [("gcc", "-std=c99"), ("gcc", "-std=gnu11"), ("g++", "-std=c++17")])
+def test_header_compiles_as_c_and_cxx(tmp_path, cc, std):
+    src = tmp_path / ("t.c" if cc == "gcc" else "t.cc")
+    src.write_text('#include "qpsk_compact.h"\n'
+                   "int main(void) { qpsk_frame_rec r = {1, 2, 3}; "
+                   "return (int)sizeof r - 16 + QPSK_REC_BY_FRAME - 1 + (int)r.bits - 3; }\n")
+    r = subprocess.run([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-fsyntax-only", "-I", INC, str(src)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
