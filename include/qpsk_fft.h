@@ -27,7 +27,10 @@ typedef struct qpsk_fft_plan qpsk_fft_plan;
 qpsk_fft_plan *qpsk_fft_alloc(int device, int nfft, int inverse, int *err);
 void qpsk_fft_free(qpsk_fft_plan *plan);
 /* fft(cfg, in, out) for `batch` transforms; device pointers, enqueued on
- * `stream` (hipStream_t, NULL = default), no synchronisation.  in may equal out. */
+ * `stream` (hipStream_t, NULL = default), no synchronisation.  in may equal out.
+ * Both pointers are 8-byte aligned (the kernel loads and stores whole complex
+ * values); any other pointer is refused with QPSK_EINVAL and nothing is
+ * launched.  Writes exactly batch * nfft complex values to d_out. */
 int qpsk_fft_device(qpsk_fft_plan *plan, const float *d_in, float *d_out, int batch, void *stream);
 /* The same from and to host memory (synchronous). */
 int qpsk_fft(qpsk_fft_plan *plan, const float *in, float *out, int batch);

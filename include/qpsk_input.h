@@ -78,7 +78,32 @@ int qpsk_rx_batch_fmt(qpsk_ctx *ctx, const void *in, int fmt, long ld, int nfram
  * the receive are enqueued on `stream`.  The converted block lives in a device
  * buffer the context owns, which only grows (a call larger than every earlier
  * one waits for the device before it reallocates).  For QPSK_IN_S16 |
- * QPSK_IN_PLANAR both calls are the plain ones: no copy, no buffer. */
+ * QPSK_IN_PLANAR both calls are the plain ones: no copy, no buffer.
+ *
+ * Pointer rules of the device receive calls (qpsk_rx_batch_device of
+ * qpsk_batch.h, this call, and the device record calls of qpsk_compact.h).
+ * The kernels load and store wider than the element types, so a device
+ * pointer needs more than its element's alignment:
+ *
+ *   d_in     16 bytes   (int4 loads; planar int16 only: a source block in
+ *                        another format follows qpsk_input_convert_device)
+ *   d_trace  16 bytes   (a frame's row is one 16-byte store)
+ *   d_soft    8 bytes   (a symbol is one 8-byte store)
+ *   d_bits    2 bytes   (a symbol's two bits are one 2-byte store)
+ *   d_valid  any
+ *
+ * A view that starts at a channel's row keeps these alignments: a frame of
+ * input is 3760 bytes, a channel-frame's rows are 62 (bits), 16 (trace) and
+ * 248 (soft) bytes.  A call with any other pointer returns QPSK_EINVAL before
+ * it touches the context or the device: nothing is launched, and
+ * qpsk_rx_frames() stays.  Host pointers (qpsk_rx_batch, qpsk_rx_batch_fmt)
+ * need no alignment.
+ *
+ * What a call writes: every byte of bits [nch][nframes][62] and valid
+ * [nch][nframes], and of trace [nch][nframes][4] and soft [nch][nframes][31][2]
+ * when given -- the zeros of invalid frames included, so the arrays need no
+ * clearing in front of a call -- and nothing else.  d_in is only read.
+ * (tests/test_gpu_rx_writeset.py holds both statements.) */
 int qpsk_rx_batch_device_fmt(qpsk_ctx *ctx, const void *d_in, int fmt, long ld, int nframes,
                              uint8_t *d_bits, uint8_t *d_valid, int32_t *d_trace,
                              float *d_soft, void *stream);

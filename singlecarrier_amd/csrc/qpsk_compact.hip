@@ -40,6 +40,7 @@
 #include "qpsk_fmt.h"
 #include "qpsk_herr.h"
 #include "qpsk_rx_internal.h"
+#include "qpsk_rx_plan.h"
 
 namespace {
 
@@ -303,6 +304,8 @@ int records_device(qpsk_ctx* c, const int16_t* d_in, int F, int order, size_t ca
                    int32_t* d_rec_trace, float* d_rec_soft, uint32_t* d_groups, uint32_t* d_count,
                    size_t out_bytes, qpsk_rec_bufs* b, hipStream_t s) {
     const int nch = qpsk_rx_channels(c);
+    // the receive's own refusal of a misaligned input (qpsk_rx_plan.h), in front of the context's buffers
+    if (F > 0 && !rx_ptrs_aligned(d_in, nullptr, nullptr, nullptr, nullptr)) return QPSK_EINVAL;
     const size_t work = qpsk_compact_work_bytes(nch, F);
     int r = qpsk_rx_rec_bufs(c, (size_t)nch * (size_t)F, d_rec_trace != nullptr, d_rec_soft != nullptr, work, out_bytes,
                              b);

@@ -79,6 +79,9 @@ extern "C" int qpsk_fft_device(qpsk_fft_plan* p, const float* d_in, float* d_out
                                void* stream) {
     if (!p || batch < 0 || (batch > 0 && (!d_in || !d_out))) return QPSK_EINVAL;
     if (batch == 0) return QPSK_OK;
+    // the kernel loads and stores whole complex values (qfft::cf, 8 bytes)
+    if (((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & (sizeof(qfft::cf) - 1)) != 0)
+        return QPSK_EINVAL;
     HCHECK(hipSetDevice(p->device));
     hipLaunchKernelGGL(fft_kernel, dim3(batch), dim3(64), sizeof(qfft::cf) * p->nfft,
                        (hipStream_t)stream, reinterpret_cast<const qfft::cf*>(d_in),

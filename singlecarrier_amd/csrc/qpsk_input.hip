@@ -38,6 +38,7 @@
 #include "qpsk_fmt_dev.h"
 #include "qpsk_herr.h"
 #include "qpsk_rx_internal.h"
+#include "qpsk_rx_plan.h"
 #include "qpsk_stream.h"
 
 namespace {
@@ -289,6 +290,8 @@ extern "C" int qpsk_rx_batch_device_fmt(qpsk_ctx* c, const void* d_in, int fmt, 
     const int nch = qpsk_rx_channels(c);
     if (qpsk_input_check(fmt, nch, F, ld) != QPSK_OK || (F > 0 && (!d_in || !d_bits || !d_valid)))
         return QPSK_EINVAL;
+    // the receive's own refusal of misaligned outputs (qpsk_rx_plan.h), in front of the conversion
+    if (F > 0 && !rx_ptrs_aligned(nullptr, d_bits, d_valid, d_trace, d_soft)) return QPSK_EINVAL;
     if (F == 0) return qpsk_rx_batch_device(c, nullptr, 0, d_bits, d_valid, d_trace, d_soft, stream);
     int16_t* conv = nullptr;
     int r = qpsk_rx_fmt_conv(c, (size_t)nch * (size_t)F * QK_FRAME, &conv);

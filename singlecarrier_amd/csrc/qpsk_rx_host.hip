@@ -699,7 +699,9 @@ int qpsk_rx_launch(qpsk_ctx* c, const int16_t* d_in, int F, uint8_t* d_bits, uin
     if (!c || F < 0 || (F > 0 && (!d_in || !d_bits || !d_valid))) return QPSK_EINVAL;
     if (c->assembly.left > 0) return QPSK_EINVAL;   // channels not yet loaded (qpsk_rx_state_load)
     if (F == 0) return QPSK_OK;
-    if ((reinterpret_cast<uintptr_t>(d_in) & 15u) != 0) return QPSK_EINVAL;  // int4 loads
+    // the kernels' loads and stores are wider than the elements (qpsk_rx_plan.h);
+    // refused before anything of the context or the device is touched
+    if (!rx_ptrs_aligned(d_in, d_bits, d_valid, d_trace, d_soft)) return QPSK_EINVAL;
     HCHECK(hipSetDevice(c->device));
     const size_t need = (size_t)c->nch * (size_t)F;   // every frame valid, at most
     // job slots are addressed with 32-bit byte offsets (slot * 16); 2^28 channel-

@@ -63,6 +63,26 @@ inline Shape pick_shape(const RxKnobs& k, int nch, int ncu) {
     return sh;
 }
 
+// ---------------------------------------------------------------- pointer alignment
+// What the receive kernels need of a call's device pointers (include/qpsk_input.h
+// "Pointer rules of the device receive calls"): the fronts load the input as
+// int4, a trace row is one int4 store, soft symbols are float2 stores and a
+// symbol's two bits one uint16_t store (back_frame, back_frame_quad,
+// rx_data_kernel); the valid flags are byte stores.  A channel's row keeps the
+// alignment: rows are 62 (bits), 16 (trace) and 248 (soft) bytes, frames 3760.
+constexpr uintptr_t kAlignIn = 16, kAlignTrace = 16, kAlignSoft = 8, kAlignBits = 2;
+static_assert(QK_NBITS % kAlignBits == 0 && (sizeof(int32_t) * 4) % kAlignTrace == 0 &&
+              (sizeof(float) * 2 * QK_NDSYM) % kAlignSoft == 0 && (sizeof(int16_t) * QK_FRAME) % kAlignIn == 0,
+              "a view that starts at a channel row keeps the alignment");
+// The alignment rule alone: a NULL pointer passes (which pointers may be NULL
+// is the entry point's own check), and valid may lie anywhere.
+inline bool rx_ptrs_aligned(const void* in, const void* bits, const void* valid, const void* trace,
+                            const void* soft) {
+    auto ok = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+    (void)valid;
+    return ok(in, kAlignIn) && ok(bits, kAlignBits) && ok(trace, kAlignTrace) && ok(soft, kAlignSoft);
+}
+
 // ---------------------------------------------------------------- staging block
 // The host-memory entry point (qpsk_rx_batch) stages a call through one block
 // [in | bits | valid | err | trace | soft]: byte offsets for cf channel-frames.

@@ -1,8 +1,11 @@
 // rx_plan_check.cc -- csrc/qpsk_rx_plan.h on the CPU (tests/test_rx_plan.py):
-// the kernel shape per batch size and forced knob, the staging layout, and the
-// snapshot size.  Built with -fsanitize=address,undefined; exits nonzero after
-// printing every check that failed.  The last lines are "state_size <n> <bytes>".
+// the kernel shape per batch size and forced knob, the staging layout, the
+// pointer alignment rule and the snapshot size.  Built with
+// -fsanitize=address,undefined; exits nonzero after printing every check that
+// failed.  Prints "limits <kZeroCopyCF> <largest pinned cf>", then the last
+// lines are "state_size <n> <bytes>".
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "qpsk_rx_plan.h"
 
@@ -100,9 +103,78 @@ static void stages() {
     CHECK(kZeroCopyCF == 64 && stage_of(kZeroCopyCF).bits <= kPinnedStage);
 }
 
+// the largest cf whose staging block is pinned (Staging::grow, rx_batch_host)
+static size_t pinned_limit() {
+    size_t cf = kPinnedStage / (sizeof(int16_t) * QK_FRAME);
+    while (stage_of(cf + 1).bits <= kPinnedStage) cf++;
+    while (stage_of(cf).bits > kPinnedStage) cf--;
+    return cf;
+}
+
+// rx_ptrs_aligned: every pointer at every byte offset of a 16-byte line, the
+// others on the line; NULL for each optional pointer; and the views of a
+// staging block, at any 16-byte aligned base, always pass.  Addresses are
+// computed as integers and cast once (no arithmetic on pointers that point
+// to no object); the views of the small blocks are taken of a real block.
+static const void* at(uintptr_t a) { return reinterpret_cast<const void*>(a); }
+
+static void pointers() {
+    const uintptr_t L = (uintptr_t)0x7f0000001000ull;
+    const void* const line = at(L);
+    CHECK(kAlignIn == 16 && kAlignTrace == 16 && kAlignSoft == 8 && kAlignBits == 2);
+    for (uintptr_t o = 0; o < 16; o++) {
+        const void* const p = at(L + o);
+        CHECK(rx_ptrs_aligned(p, line, line, line, line) == (o % 16 == 0));      // in
+        CHECK(rx_ptrs_aligned(line, p, line, line, line) == (o % 2 == 0));       // bits
+        CHECK(rx_ptrs_aligned(line, line, p, line, line));                       // valid: any
+        CHECK(rx_ptrs_aligned(line, line, line, p, line) == (o % 16 == 0));      // trace
+        CHECK(rx_ptrs_aligned(line, line, line, line, p) == (o % 8 == 0));       // soft
+        // absent optional outputs change nothing for the others
+        CHECK(rx_ptrs_aligned(line, p, line, nullptr, nullptr) == (o % 2 == 0));
+        CHECK(rx_ptrs_aligned(line, line, line, nullptr, p) == (o % 8 == 0));
+        CHECK(rx_ptrs_aligned(line, line, line, p, nullptr) == (o % 16 == 0));
+        CHECK(rx_ptrs_aligned(nullptr, line, p, nullptr, nullptr));
+    }
+    CHECK(rx_ptrs_aligned(nullptr, nullptr, nullptr, nullptr, nullptr));
+    // the minimum legal placement of each array past a 16-byte line, together
+    CHECK(rx_ptrs_aligned(line, at(L + 2), at(L + 1), at(L + 16), at(L + 8)));
+    // a channel's row of aligned arrays stays aligned (62, 16, 248, 3760-byte rows)
+    for (uintptr_t cf : {(uintptr_t)1, (uintptr_t)3, (uintptr_t)1000001})
+        CHECK(rx_ptrs_aligned(at(L + cf * sizeof(int16_t) * QK_FRAME), at(L + 2 + cf * QK_NBITS), at(L + 1 + cf),
+                              at(L + cf * 16), at(L + 8 + cf * sizeof(float) * 2 * QK_NDSYM)));
+    // the sections of a block at any 16-byte aligned base (StageView's pointers
+    // are base + offset: stages() above)
+    auto sections_ok = [&](size_t cf) {
+        const Stage g = stage_of(cf);
+        for (uintptr_t B : {L, L + 256, L + 16}) {
+            CHECK(rx_ptrs_aligned(at(B + g.in), at(B + g.bits), at(B + g.valid), at(B + g.trace), at(B + g.soft)));
+            CHECK(rx_ptrs_aligned(at(B + g.in), at(B + g.bits), at(B + g.valid), nullptr, at(B + g.soft)));
+            CHECK((B + g.err) % sizeof(int) == 0);
+        }
+        CHECK(g.in % kAlignIn == 0 && g.bits % kAlignBits == 0 && g.trace % kAlignTrace == 0 &&
+              g.soft % kAlignSoft == 0);
+    };
+    // the views themselves, of a real block as hipMalloc aligns it
+    char* const block = static_cast<char*>(aligned_alloc(256, stage_of(70).end));
+    CHECK(block != nullptr);
+    for (size_t cf = 1; cf <= 70; cf++) {
+        sections_ok(cf);
+        if (!block) continue;
+        const StageView v{block, stage_of(cf)};
+        CHECK(rx_ptrs_aligned(v.in(), v.bits(), v.valid(), v.trace(), v.soft()));
+        CHECK(rx_ptrs_aligned(v.in(), v.bits(), v.valid(), nullptr, nullptr));
+    }
+    free(block);
+    const size_t lim = pinned_limit();
+    CHECK(stage_of(lim).bits <= kPinnedStage && stage_of(lim + 1).bits > kPinnedStage);
+    for (size_t cf : {lim - 1, lim, lim + 1, (size_t)65536 * 32}) sections_ok(cf);
+    printf("limits %zu %zu\n", (size_t)kZeroCopyCF, lim);
+}
+
 int main() {
     shapes();
     stages();
+    pointers();
     for (int n : {0, -3, 1, 96, 65536}) printf("state_size %d %zu\n", n, rx_state_size(n));
     return g_fail ? 1 : 0;
 }

@@ -218,6 +218,33 @@ def test_pack_device_equals_the_host_packer():
     assert sc.pack_bits_device(torch.zeros((0, 62), dtype=torch.uint8, device="cuda")).shape == (0,)
 
 
+@pytest.mark.parametrize("n", [1, 5])
+def test_pack_device_writes_its_words_and_nothing_else(n):
+    """d_words 8 bytes past a 16-byte line (its stated alignment) inside a
+    sentinel-filled buffer, 256 guard bytes on both sides: n words are written,
+    the guards stay.  A pointer 4 bytes further is refused."""
+    import torch
+    guard = 256
+    rng = np.random.default_rng(40 + n)
+    bits = rng.integers(0, 2, (n, 62), dtype=np.uint8)
+    d_bits = torch.from_numpy(bits).cuda()
+    for fill in (SENT, SENT ^ 0xFF):
+        raw = torch.full((2 * guard + 8 * n + 32,), fill, dtype=torch.uint8, device="cuda")
+        base = (-raw.data_ptr()) % 16
+        buf = raw[base:base + 2 * guard + 8 * n + 8]
+        off = guard + 8
+        assert (buf.data_ptr() + off) % 16 == 8
+        img = np.full(buf.numel(), fill, np.uint8)
+        rc = sc.lib().qpsk_bits_pack_device(d_bits.data_ptr(), n, buf.data_ptr() + off + 4, None)
+        assert rc == sc.QPSK_EINVAL
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(buf.cpu().numpy(), img)
+        sc.pack_bits_device(d_bits, out=buf[off:off + 8 * n].view(torch.int64))
+        torch.cuda.synchronize()
+        img[off:off + 8 * n] = sc.pack_bits(bits).view(np.uint8)
+        np.testing.assert_array_equal(buf.cpu().numpy(), img)
+
+
 @pytest.mark.parametrize("order", ORDERS)
 def test_offsets_past_32_bits(order):
     """70 M items: an item's bits row starts past 2^32 bytes (62 * n = 4.3 GB).

@@ -49,6 +49,48 @@ def test_fft_large_batch_in_place_on_device():
     np.testing.assert_array_equal(got.view(np.uint32), ref.view(np.uint32))
 
 
+@pytest.mark.parametrize("in_place", [False, True], ids=["out-of-place", "in-place"])
+@pytest.mark.parametrize("n", [4, 256])
+def test_fft_device_writes_its_output_and_nothing_else(n, in_place):
+    """qpsk_fft_device casts its float pointers to complex ones: 8-byte
+    alignment is what it needs (include/qpsk_fft.h).  Input and output lie 8
+    bytes past a 16-byte line inside one sentinel-filled buffer with 256 guard
+    bytes around each; the whole buffer is compared with the host's image.  A
+    pointer 4 bytes further is refused and nothing is written."""
+    import torch
+    batch, guard = 3, 256
+    x = _cases(n, 4, 100 + n)[:batch]
+    ref = oracle.cpu_fft(x)
+    nb = x.nbytes
+    o_in = guard + 8
+    o_out = o_in if in_place else (o_in + nb + guard + 15) // 16 * 16 + 8
+    total = o_out + nb + guard
+    plan = sc.FftPlan(n)
+    for fill in (0xA5, 0x5A):
+        raw = torch.full((total + 16,), fill, dtype=torch.uint8, device="cuda")
+        base = (-raw.data_ptr()) % 16
+        buf = raw[base:base + total]
+        assert (buf.data_ptr() + o_in) % 16 == 8 and (buf.data_ptr() + o_out) % 16 == 8
+        buf[o_in:o_in + nb].copy_(torch.from_numpy(x.view(np.uint8).reshape(-1).copy()))
+        img = np.full(total, fill, np.uint8)
+        img[o_in:o_in + nb] = x.view(np.uint8).reshape(-1)
+
+        def f32(o):
+            return buf[o:o + nb].view(torch.float32)
+
+        for sh_in, sh_out in ((4, 0), (0, 4), (4, 4)):
+            with pytest.raises(sc.QpskError) as e:
+                plan.run_device(f32(o_in + sh_in), f32(o_out + sh_out))
+            assert e.value.code == sc.QPSK_EINVAL
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(buf.cpu().numpy(), img)
+        plan.run_device(f32(o_in), f32(o_out))
+        torch.cuda.synchronize()
+        img[o_out:o_out + nb] = ref.view(np.uint8).reshape(-1)
+        np.testing.assert_array_equal(buf.cpu().numpy(), img)
+    plan.close()
+
+
 # ------------------------------------------------- the FFT-correlation hunt variant
 # QPSK_MODE_FFT_HUNT (flag): the receiver's hunt correlates through kiss_fft.
 # Expected values: the oracle restatement's same mode (its hunt pinned to the

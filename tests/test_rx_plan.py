@@ -1,7 +1,8 @@
 """The receive path's host decisions on the CPU (csrc/qpsk_rx_plan.h): which
 rx_kernel instantiation a batch gets (thresholds of DESIGN.md "Kernels" on a
 256-CU device, forced shape, width and priority), the layout of the
-host-memory entry point's staging block, and the snapshot size.  The header
+host-memory entry point's staging block, the alignment rule of a receive call's
+device pointers, and the snapshot size.  The header
 makes no HIP runtime call, so tests/sanitize/rx_plan_check.cc is built with
 plain g++ under ASan + UBSan and run here; any report or failed check fails
 the test.  CPU only."""
@@ -16,13 +17,20 @@ CSRC = os.path.join(ROOT, "singlecarrier_amd", "csrc")
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
 
 
-@pytest.fixture(scope="module")
-def plan_out(tmp_path_factory):
+def run_plan_check(tmp_dir, sanitize=True) -> str:
+    """Build tests/sanitize/rx_plan_check.cc in tmp_dir, run it and return
+    what it printed.  sanitize: under ASan + UBSan, as the tests of this file
+    run it (skipped without g++).  tests/test_gpu_rx_writeset.py reads the
+    staging limits from a plain build (sanitize=False: sanitizers stay out of
+    the GPU suite; a missing compiler fails there, it does not skip)."""
     if shutil.which("g++") is None:
-        pytest.skip("g++ not available")
-    exe = str(tmp_path_factory.mktemp("plan") / "rx_plan_check")
+        if sanitize:
+            pytest.skip("g++ not available")
+        pytest.fail("g++ not available: the staging limits come from csrc/qpsk_rx_plan.h")
+    exe = str(tmp_dir / "rx_plan_check")
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", *SAN, "-D__HIP_PLATFORM_AMD__",
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", *(SAN if sanitize else []),
+                    "-D__HIP_PLATFORM_AMD__",
                     "-I" + os.path.join(rocm, "include"), "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
                     "-o", exe, os.path.join(ROOT, "tests", "sanitize", "rx_plan_check.cc")], check=True)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
@@ -31,6 +39,19 @@ def plan_out(tmp_path_factory):
     assert r.returncode == 0, f"rx_plan_check failed ({r.returncode}):\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
     return r.stdout
+
+
+def plan_limits(out: str):
+    """(kZeroCopyCF, the largest cf whose staging block is pinned) from the
+    program's "limits" line."""
+    (line,) = [l for l in out.splitlines() if l.startswith("limits ")]
+    zero_copy, pinned = (int(v) for v in line.split()[1:])
+    return zero_copy, pinned
+
+
+@pytest.fixture(scope="module")
+def plan_out(tmp_path_factory):
+    return run_plan_check(tmp_path_factory.mktemp("plan"))
 
 
 def test_shapes_and_staging_layout(plan_out):
@@ -46,3 +67,16 @@ def test_state_size_matches_the_abi_formula(plan_out):
     per = 2 * 1880 * 2 + 168 * 8 + 4 + 4
     got = {int(l.split()[1]): int(l.split()[2]) for l in plan_out.splitlines() if l.startswith("state_size")}
     assert got == {0: 0, -3: 0, 1: 64 + per, 96: 64 + 96 * per, 65536: 64 + 65536 * per}
+
+
+def test_pointer_rule_and_staging_views(plan_out):
+    """rx_ptrs_aligned at every offset 0..15 of each pointer and with the
+    optional ones NULL, and the views of stage_of(cf) for cf = 1..70 and around
+    the pinned limit (pointers() of the program: a failed check prints FAILED
+    with its line).  The limits it prints are the ones the host-call cases of
+    tests/test_gpu_rx_writeset.py sit at."""
+    assert "FAILED" not in plan_out
+    zero_copy, pinned = plan_limits(plan_out)
+    assert zero_copy == 64
+    # 3760 bytes of input per channel-frame, rounded up to 256, within 8 MiB
+    assert -(-3760 * pinned // 256) * 256 <= 8 << 20 < -(-3760 * (pinned + 1) // 256) * 256
