@@ -139,7 +139,13 @@ int qpsk_rx_state_load(qpsk_ctx *ctx, int c0, int n, const void *buf, size_t siz
 
 /* Host-memory call: copies `in` to the device, demodulates nframes frames of
  * every channel, copies the results back and synchronises; returns
- * qpsk_rx_sync()'s verdict. */
+ * qpsk_rx_sync()'s verdict.  It runs on a stream of the context's own, which
+ * a caller cannot chain behind theirs, so it orders itself: a device call of
+ * the context that is still pending on a caller's stream is waited for first
+ * (as qpsk_rx_reset and the state calls do), and the call continues from the
+ * state that one leaves.  The same holds for every host-memory form
+ * (qpsk_rx_batch_fmt, qpsk_rx_batch_records, qpsk_rx_batch_records_fmt).
+ * After host calls alone there is nothing to wait for, and nothing is. */
 int qpsk_rx_batch(qpsk_ctx *ctx, const int16_t *in, int nframes, uint8_t *bits,
                   uint8_t *valid, int32_t *trace, float *soft);
 
@@ -147,13 +153,23 @@ int qpsk_rx_batch(qpsk_ctx *ctx, const int16_t *in, int nframes, uint8_t *bits,
  * the work is enqueued on `stream` (a hipStream_t, NULL = default stream) and
  * the call returns without synchronising.  Launches two kernels: rx_kernel
  * (every stage of every frame, persistent over the call's frames) and
- * rx_data_kernel (the 31 data symbols of the valid frames); see DESIGN.md. */
+ * rx_data_kernel (the 31 data symbols of the valid frames); see DESIGN.md.
+ * The one exception to "without synchronising": the context's job queue (and
+ * the head pre-pass buffer) is sized by its largest call so far, and a call
+ * with more channel-frames than any before it on the context waits for the
+ * whole device (earlier calls may still use the buffers) while they are
+ * reallocated.  A first call of the largest size, before the timed or
+ * latency-bound part, leaves every later call free of that wait.  The fmt and
+ * record device forms (qpsk_input.h, qpsk_compact.h) say the same of their
+ * buffers.  (tests/test_gpu_async.py holds the stream order of every device
+ * call, with work still in flight on the stream.) */
 int qpsk_rx_batch_device(qpsk_ctx *ctx, const int16_t *d_in, int nframes,
                          uint8_t *d_bits, uint8_t *d_valid, int32_t *d_trace,
                          float *d_soft, void *stream);
 
 /* Waits for the context's latest qpsk_rx_batch_device call (an event recorded
- * on its stream after its kernels; the stream itself may since be destroyed)
+ * on its stream after its kernels, and after the compaction of a device record
+ * call; the stream itself may since be destroyed)
  * and returns QPSK_ESTALL if any call since the previous check reported a
  * device-side failure, else 0.  The device error word is sticky until this
  * reads it, and is read and cleared in one atomic exchange.  Calls on one

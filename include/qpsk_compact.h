@@ -115,8 +115,11 @@ int qpsk_rx_batch_records_fmt(qpsk_ctx *ctx, const void *in, int fmt, long ld, i
                               int order, size_t cap, qpsk_frame_rec *rec, int32_t *rec_trace,
                               float *rec_soft, uint32_t *groups, uint32_t *count);
 /* The asynchronous device form: all pointers are device pointers, the receive
- * and the compaction are enqueued on `stream`; check with qpsk_rx_sync.  The
- * dense intermediates and the work area are grow-only buffers of the context. */
+ * and the compaction are enqueued on `stream`; check with qpsk_rx_sync, which
+ * waits for the compaction too.  The dense intermediates and the work area are
+ * grow-only buffers of the context: like qpsk_rx_batch_device the call returns
+ * without synchronising, except that a call larger than every earlier one on
+ * the context waits for the whole device before it reallocates them. */
 int qpsk_rx_batch_records_device(qpsk_ctx *ctx, const int16_t *d_in, int nframes, int order,
                                  size_t cap, qpsk_frame_rec *d_rec, int32_t *d_rec_trace,
                                  float *d_rec_soft, uint32_t *d_groups, uint32_t *d_count,

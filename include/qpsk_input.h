@@ -76,9 +76,11 @@ int qpsk_rx_batch_fmt(qpsk_ctx *ctx, const void *in, int fmt, long ld, int nfram
 
 /* qpsk_rx_batch_device() for device input in format `fmt`: the conversion and
  * the receive are enqueued on `stream`.  The converted block lives in a device
- * buffer the context owns, which only grows (a call larger than every earlier
- * one waits for the device before it reallocates).  For QPSK_IN_S16 |
- * QPSK_IN_PLANAR both calls are the plain ones: no copy, no buffer.
+ * buffer the context owns, which only grows: like qpsk_rx_batch_device it
+ * returns without synchronising, except that a call larger than every earlier
+ * one on the context waits for the whole device before it reallocates.  For
+ * QPSK_IN_S16 | QPSK_IN_PLANAR both calls are the plain ones: no copy, no
+ * buffer.
  *
  * Pointer rules of the device receive calls (qpsk_rx_batch_device of
  * qpsk_batch.h, this call, and the device record calls of qpsk_compact.h).

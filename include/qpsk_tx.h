@@ -54,12 +54,24 @@ uint64_t qpsk_tx_packets(const qpsk_tx_ctx *ctx);
  * bits or out with npackets > 0 (and a NULL context).
  *
  * qpsk_tx_batch: host memory; copies in, modulates, copies the written
- * samples back and synchronises. */
+ * samples back and synchronises.  It runs on a stream of the context's own,
+ * which a caller cannot chain behind theirs, so it orders itself: a
+ * qpsk_tx_batch_device call still pending on a caller's stream is waited for
+ * first (as qpsk_tx_reset does), and the call continues the stream from the
+ * state that one leaves.  qpsk_tx_batch_fmt (qpsk_output.h) does the same. */
 int qpsk_tx_batch(qpsk_tx_ctx *ctx, const uint8_t *bits, int npackets, int16_t *out, long ld);
 /* Device memory on the context's device; the work is enqueued on `stream` (a
  * hipStream_t, NULL = default stream) and the call does not wait for the
  * kernel.  Calls on one context depend on each other through the carried
- * state, so the caller orders them (one stream, or streams it chains). */
+ * state, so the caller orders them (one stream, or streams it chains).
+ * Two things can make a call wait.  The carrier of a call's samples is built
+ * on the host in one of two pinned staging slots and uploaded on `stream`: a
+ * call finds a free slot as long as at most one earlier call's upload is
+ * still pending, so two calls in a row never wait for each other, and a third
+ * waits until the first one's upload has run.  And a call of more packets
+ * than any before it on the context reallocates the carrier table and the
+ * slot, which waits for the whole device (earlier calls may still read them);
+ * a first call of the largest size leaves every later call free of that. */
 int qpsk_tx_batch_device(qpsk_tx_ctx *ctx, const uint8_t *d_bits, int npackets,
                          int16_t *d_out, long ld, void *stream);
 /* Waits for the context's latest qpsk_tx_batch_device call. */

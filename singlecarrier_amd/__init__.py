@@ -293,6 +293,14 @@ def _stream(stream, device):
     return C.c_void_p(stream.cuda_stream)
 
 
+def _on(stream, device):
+    """The torch stream context of a device call: ``stream``, or torch's current
+    stream on `device`.  A wrapper allocates the tensors it makes inside it, so
+    their memory belongs to the stream the call is enqueued on."""
+    import torch
+    return torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(device))
+
+
 def _fmt_check(fmt: int, nch: int) -> None:
     """QPSK_EINVAL for an unknown format word or nch < 1 (the library's own
     check: a call of no frames)."""
@@ -380,12 +388,12 @@ def input_convert_device(x, fmt: int, nch: int, out=None, stream=None):
     import torch
     _fmt_check(fmt, nch)
     nf, ld = _torch_block(x, fmt, nch)
-    if out is None:
-        out = torch.empty((nch, nf, FRAME_SIZE), dtype=torch.int16, device=x.device)
-    elif out.dtype != torch.int16 or tuple(out.shape) != (nch, nf, FRAME_SIZE) or not out.is_contiguous() \
-            or not out.is_cuda:
+    if out is not None and (out.dtype != torch.int16 or tuple(out.shape) != (nch, nf, FRAME_SIZE)
+                            or not out.is_contiguous() or not out.is_cuda):
         raise ValueError(f"out must be a contiguous cuda int16 [{nch}][{nf}][{FRAME_SIZE}] tensor")
-    with torch.cuda.device(x.device):
+    with torch.cuda.device(x.device), _on(stream, x.device):
+        if out is None:
+            out = torch.empty((nch, nf, FRAME_SIZE), dtype=torch.int16, device=x.device)
         _check(lib().qpsk_input_convert_device(fmt, x.data_ptr(), ld, nch, nf, out.data_ptr(),
                                                _stream(stream, x.device)))
     return out
@@ -541,9 +549,9 @@ def pack_bits_device(bits, out=None, stream=None):
     import torch
     if not bits.is_cuda or bits.dtype != torch.uint8 or bits.shape[-1] != NBITS or not bits.is_contiguous():
         raise ValueError(f"bits must be a contiguous cuda uint8 [...][{NBITS}] tensor")
-    if out is None:
-        out = torch.empty(tuple(bits.shape[:-1]), dtype=torch.int64, device=bits.device)
-    with torch.cuda.device(bits.device):
+    with torch.cuda.device(bits.device), _on(stream, bits.device):
+        if out is None:
+            out = torch.empty(tuple(bits.shape[:-1]), dtype=torch.int64, device=bits.device)
         _check(lib().qpsk_bits_pack_device(bits.data_ptr(), out.numel(), out.data_ptr(),
                                            _stream(stream, bits.device)))
     return out
@@ -612,19 +620,19 @@ def compact_device(bits, valid, trace=None, soft=None, order: int = REC_BY_CHANN
     nch, nf = tuple(valid.shape)
     dev = valid.device
     cap = nch * nf if cap is None else int(cap)
-    if rec is None and cap > 0:
-        rec = torch.empty((cap, 2), dtype=torch.int64, device=dev)
-    if rec_trace is None and trace is not None:
-        rec_trace = torch.empty((cap, 4), dtype=torch.int32, device=dev)
-    if rec_soft is None and soft is not None:
-        rec_soft = torch.empty((cap, DATA_SYMBOLS, 2), dtype=torch.float32, device=dev)
-    if groups is None:
-        groups = torch.empty(_groups_of(order, nch, nf) + 1, dtype=torch.int32, device=dev)
-    if count is None:
-        count = torch.empty(1, dtype=torch.int32, device=dev)
-    if work is None:
-        work = torch.empty(compact_work_bytes(nch, nf), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), _on(stream, dev):
+        if rec is None and cap > 0:
+            rec = torch.empty((cap, 2), dtype=torch.int64, device=dev)
+        if rec_trace is None and trace is not None:
+            rec_trace = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+        if rec_soft is None and soft is not None:
+            rec_soft = torch.empty((cap, DATA_SYMBOLS, 2), dtype=torch.float32, device=dev)
+        if groups is None:
+            groups = torch.empty(_groups_of(order, nch, nf) + 1, dtype=torch.int32, device=dev)
+        if count is None:
+            count = torch.empty(1, dtype=torch.int32, device=dev)
+        if work is None:
+            work = torch.empty(compact_work_bytes(nch, nf), dtype=torch.uint8, device=dev)
         _check(lib().qpsk_compact_device(_ptr(bits), _ptr(valid), _ptr(trace), _ptr(soft), nch, nf, order, cap,
                                          _ptr(rec), _ptr(rec_trace), _ptr(rec_soft), _ptr(groups), _ptr(count),
                                          _ptr(work), work.numel(), _stream(stream, dev)))
@@ -807,7 +815,7 @@ class Receiver:
         nf = x.shape[1]
         cap = self.nch * nf if cap is None else int(cap)
         dev = x.device
-        with torch.cuda.device(dev), torch.cuda.stream(stream or torch.cuda.current_stream(dev)):
+        with torch.cuda.device(dev), _on(stream, dev):
             rec = torch.empty((cap, 2), dtype=torch.int64, device=dev) if cap > 0 else None
             rtr = torch.empty((cap, 4), dtype=torch.int32, device=dev) if trace else None
             rso = torch.empty((cap, DATA_SYMBOLS, 2), dtype=torch.float32, device=dev) if soft else None
@@ -1192,11 +1200,11 @@ class FftPlan:
     def run_device(self, x, out=None, stream=None):
         """torch complex64 (or float32 [..., nfft, 2]) cuda tensors; enqueued."""
         import torch
-        if out is None:
-            out = torch.empty_like(x)
         n = x.numel() // (self.nfft * (1 if x.is_complex() else 2))
-        s = stream if stream is not None else torch.cuda.current_stream(x.device)
-        _check(lib().qpsk_fft_device(self._h, x.data_ptr(), out.data_ptr(), n, s.cuda_stream))
+        with torch.cuda.device(x.device), _on(stream, x.device):
+            if out is None:
+                out = torch.empty_like(x)
+            _check(lib().qpsk_fft_device(self._h, x.data_ptr(), out.data_ptr(), n, _stream(stream, x.device)))
         return out
 
 

@@ -323,8 +323,12 @@ int records_device(qpsk_ctx* c, const int16_t* d_in, int F, int order, size_t ca
     }
     // (F == 0: no receive was launched and the dense buffers may be empty; the
     // compaction of no items reads none of them)
-    return qpsk_compact_device(b->bits, b->valid, b->trace, b->soft, nch, F, order, cap, d_rec,
-                               d_rec_trace, d_rec_soft, d_groups, d_count, b->work, work, s);
+    r = qpsk_compact_device(b->bits, b->valid, b->trace, b->soft, nch, F, order, cap, d_rec,
+                            d_rec_trace, d_rec_soft, d_groups, d_count, b->work, work, s);
+    if (r != QPSK_OK || F == 0) return r;
+    // the compaction reads the context's dense buffers: whoever waits for the
+    // context's latest call (qpsk_rx_sync, a host call) waits for it too
+    return qpsk_rx_mark(c, s);
 }
 
 struct HostIn {
@@ -345,6 +349,10 @@ int records_host(qpsk_ctx* c, const HostIn& hi, int F, int order, size_t cap, qp
     const size_t G = (size_t)(order == QPSK_REC_BY_FRAME ? F : nch);
     const size_t m = cap < cf ? cap : cf;   // rows there can be
     hipStream_t s = qpsk_rx_stream(c);
+    // a device call still pending on a caller's stream uses the buffers taken
+    // below (a call of no frames still compacts in the context's work area)
+    r = qpsk_rx_wait_pending(c);
+    if (r != QPSK_OK) return r;
     int16_t* d_in = nullptr;
     if (F > 0) {
         r = qpsk_rx_fmt_conv(c, cf * QK_FRAME, &d_in);

@@ -310,6 +310,9 @@ extern "C" int qpsk_tx_batch_fmt(qpsk_tx_ctx* c, const uint8_t* bits, int npacke
     const int chk = tx_fmt_check(c, bits, npackets, out, fmt, ld, &N);
     if (chk != QPSK_OK || npackets == 0) return chk;
     HCHECK(hipSetDevice(qpsk_tx_device(c)));
+    // a device call still pending on a caller's stream (qpsk_tx_batch waits alike)
+    const int pend = qpsk_tx_sync(c);
+    if (pend != QPSK_OK) return pend;
     hipStream_t s = (hipStream_t)qpsk_tx_host_stream(c);
     const int nch = qpsk_tx_channels(c);
     const size_t es = (size_t)qpsk_fmt_esize(fmt);

@@ -310,6 +310,11 @@ struct qpsk_ctx {
                                 // [1] the value it took
     qhip::Event done;           // recorded after the latest call's kernels, on its stream
     bool called = false;        // `done` has been recorded
+    // `done` was last recorded on a caller's stream: a host-memory call, which
+    // runs on the context's own, waits for it first (qpsk_rx_wait_pending).
+    // Host calls synchronise their stream before they return, so after one of
+    // them there is nothing left to wait for.
+    bool pending = false;
     RxLaunch base{};            // a call's launches, all that never changes filled in
     uint64_t frames = 0;
     uint64_t calls = 0;
@@ -685,6 +690,19 @@ extern "C" void qpsk_rx_destroy(qpsk_ctx* c) {
     delete c;
 }
 
+// Internal, not part of the C-ABI in include/ (tests: a context made under
+// QPSK_SHAPE / QPSK_WIDTH / QPSK_HEADPASS launches what the knobs name): the
+// rx_kernel shape of the context's calls, "+head" with the head pre-pass.
+extern "C" const char* qpsk_rx_plan_name(const qpsk_ctx* c) {
+    if (!c) return "";
+    static const char* const names[2][5] = {{"4x2", "2x4d", "1x8d64", "1x8q16", "1x8q32"},
+                                            {"4x2+head", "2x4d+head", "1x8d64+head", "1x8q16+head", "1x8q32+head"}};
+    static_assert(Shape::k4x2 == 0 && Shape::k2x4d == 1 && Shape::k1x8d64 == 2 && Shape::k1x8q16 == 3 &&
+                  Shape::k1x8q32 == 4, "names follow Shape::Kind");
+    const int kind = pick_shape(c->knobs, c->nch, c->ncu).kind;
+    return kind >= 0 && kind < 5 ? names[c->knobs.headpass ? 1 : 0][kind] : "";
+}
+
 extern "C" int qpsk_rx_channels(const qpsk_ctx* c) { return c ? c->nch : 0; }
 extern "C" int qpsk_rx_mode(const qpsk_ctx* c) { return c ? c->mode : QPSK_EINVAL; }
 extern "C" uint64_t qpsk_rx_frames(const qpsk_ctx* c) { return c ? c->frames : 0; }
@@ -740,6 +758,7 @@ int qpsk_rx_launch(qpsk_ctx* c, const int16_t* d_in, int F, uint8_t* d_bits, uin
     if (lr != QPSK_OK) return lr;
     HCHECK(hipEventRecord(c->done, s));
     c->called = true;
+    c->pending = s != (hipStream_t)c->stream;
     c->frames += (uint64_t)F;
     c->calls++;
     c->launches++;
@@ -751,6 +770,28 @@ extern "C" int qpsk_rx_batch_device(qpsk_ctx* c, const int16_t* d_in, int F, uin
                                     void* stream) {
     return qpsk_rx_launch(c, d_in, F, d_bits, d_valid, d_trace, d_soft, (hipStream_t)stream,
                           nullptr, nullptr);
+}
+
+// qpsk_rx_internal.h: what follows a call's kernels on s and still uses the
+// context's buffers (a record call's compaction) is covered by `done` too
+int qpsk_rx_mark(qpsk_ctx* c, hipStream_t s) {
+    if (!c) return QPSK_EINVAL;
+    HCHECK(hipEventRecord(c->done, s));
+    c->called = true;
+    c->pending = s != (hipStream_t)c->stream;
+    return QPSK_OK;
+}
+
+// qpsk_rx_internal.h: a device call still pending on a caller's stream writes
+// the per-channel state, the job queue and the context's format and record
+// buffers, which a host-memory call on the context's own stream is about to use
+int qpsk_rx_wait_pending(qpsk_ctx* c) {
+    if (!c) return QPSK_EINVAL;
+    if (!c->pending) return QPSK_OK;
+    HCHECK(hipSetDevice(c->device));
+    HCHECK(hipEventSynchronize(c->done));
+    c->pending = false;
+    return QPSK_OK;
 }
 
 // Waits for the context's latest call (an event recorded on its stream, so the
@@ -800,7 +841,11 @@ static int rx_batch_host(qpsk_ctx* c, const int16_t* in, qpsk_rx_feed_fn feed, v
     if (c->assembly.left > 0) return QPSK_EINVAL;   // channels not yet loaded (qpsk_rx_state_load)
     if (F == 0) return QPSK_OK;
     HCHECK(hipSetDevice(c->device));
-    int r = c->stage.grow(c->nch, (size_t)F);
+    // a device call still pending on a caller's stream: this call continues
+    // from the state it leaves
+    int r = qpsk_rx_wait_pending(c);
+    if (r != QPSK_OK) return r;
+    r = c->stage.grow(c->nch, (size_t)F);
     if (r != QPSK_OK) return r;
     const size_t cf = (size_t)c->nch * F;
     const Stage g = stage_of(cf);

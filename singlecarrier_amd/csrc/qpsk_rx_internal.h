@@ -75,6 +75,15 @@ int qpsk_rx_rec_bufs(qpsk_ctx* c, size_t cf, bool trace, bool soft, size_t work_
                      qpsk_rec_bufs* b);
 // the context's own stream (what its host calls run on)
 hipStream_t qpsk_rx_stream(qpsk_ctx* c);
+// What qpsk_rx_sync(), the reset and state calls and the host-memory calls
+// wait for moves behind the work enqueued on s so far: the compaction that
+// follows a record call's receive and still reads the context's buffers.
+int qpsk_rx_mark(qpsk_ctx* c, hipStream_t s);
+// Waits for the context's latest device call if it went to a caller's stream:
+// every host-memory entry point that runs on the context's own stream calls
+// this before it touches the per-channel state or a buffer of the context
+// (qpsk_rx_batch and qpsk_rx_batch_fed do so themselves).
+int qpsk_rx_wait_pending(qpsk_ctx* c);
 // A stream whose chunks come back through a post-receive pass: submit runs
 // `compact` on the receive stream behind the receive, on the slot's dense
 // bits / valid, and copies back the count and the groups (uint32 [1 + ngroups

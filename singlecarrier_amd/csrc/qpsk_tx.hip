@@ -468,6 +468,10 @@ extern "C" int qpsk_tx_batch(qpsk_tx_ctx* c, const uint8_t* bits, int npackets, 
     const int chk = tx_check(c, bits, npackets, out, ld);
     if (chk != QPSK_OK || npackets == 0) return chk;
     HCHECK(hipSetDevice(c->device));
+    // A device call still pending on a caller's stream leaves the 9 dibits this
+    // call filters over and reads the carrier table this call replaces; the
+    // context's own stream cannot be chained behind it from outside.
+    HCHECK(hipEventSynchronize(c->ev_last));
     const size_t nbits = (size_t)c->nch * (size_t)npackets * kPacketBits;
     const size_t N = (size_t)npackets * (size_t)(kTxPacket + (long)c->gap);
     qhip::DevBuf<uint8_t> d_bits;   // released on return, after the synchronisation
