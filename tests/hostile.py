@@ -29,6 +29,9 @@ import os
 
 import numpy as np
 
+import oracle
+from rxcheck import frozen
+
 FRAME = 1880
 NFRAMES = 12
 PARAMS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hostile_params.json")
@@ -97,7 +100,6 @@ def waves(rows=None, nframes=NFRAMES):
 
 def impaired(rows=None, nframes=NFRAMES):
     """The "impaired" group [nch][nframes][1880] int16."""
-    import oracle
     rows = params()["impaired"] if rows is None else rows
     out = []
     for r in rows:
@@ -106,30 +108,13 @@ def impaired(rows=None, nframes=NFRAMES):
     return np.stack(out)
 
 
-def _frozen(*arrays):
-    for a in arrays:
-        if a is not None:
-            a.setflags(write=False)
-    return arrays
-
-
 @functools.lru_cache(maxsize=None)
 def group(name):
     """A group's samples at the table's frame count, made once, read-only."""
-    return _frozen(waves() if name == "wave" else impaired())[0]
+    return frozen(waves() if name == "wave" else impaired())[0]
 
 
 @functools.lru_cache(maxsize=None)
 def expected(name, mode=0):
     """The oracle's (bits, valid, trace) for a group, computed once, read-only."""
-    import oracle
-    return _frozen(*oracle.cpu_rx(group(name), trace=True, mode=mode))
-
-
-def same_soft(got, exp):
-    """Soft symbols as the GPU tests compare them: finite values and infinities
-    bit for bit, NaN as a class (a GPU's NaN payloads and signs need not be
-    x86's).  Returns the mask of differing elements."""
-    got, exp = np.asarray(got, np.float32), np.asarray(exp, np.float32)
-    nan = np.isnan(exp)
-    return np.where(nan, ~np.isnan(got), got.view(np.uint32) != exp.view(np.uint32))
+    return frozen(*oracle.cpu_rx(group(name), trace=True, mode=mode))

@@ -59,6 +59,7 @@ import numpy as np
 
 import oracle
 import timing
+from rxcheck import frozen
 
 FRAME = 1880
 NFRAMES = 12
@@ -92,20 +93,13 @@ TAILS = ((3, 758, 900, 24, 19, 99), (0, 787, 900, 24, 9, 35), (1, 645, 900, -51,
 NTAIL = 32
 
 
-def _frozen(*arrays):
-    for a in arrays:
-        if a is not None:
-            a.setflags(write=False)
-    return arrays
-
-
 @functools.lru_cache(maxsize=None)
 def bursts():
     """[NBURST][BURST_LEN] int32: the head of each of the base stream's packets."""
     b = timing.base(6)
     assert b.size >= (NBURST - 1) * timing.PERIOD + BURST_LEN
     out = np.stack([b[j * timing.PERIOD:j * timing.PERIOD + BURST_LEN] for j in range(NBURST)])
-    return _frozen(out.astype(np.int32))[0]
+    return frozen(out.astype(np.int32))[0]
 
 
 class _Lcg:
@@ -269,13 +263,13 @@ def group_slices():
 def corpus():
     rows = [r for fn in GROUPS.values() for r in fn()]
     assert len(rows) <= 8192
-    return _frozen(render(rows))[0]
+    return frozen(render(rows))[0]
 
 
 @functools.lru_cache(maxsize=None)
 def expected(mode=0):
     """The oracle's (bits, valid, trace) over the corpus, computed once, read-only."""
-    return _frozen(*oracle.cpu_rx(corpus(), trace=True, mode=mode))
+    return frozen(*oracle.cpu_rx(corpus(), trace=True, mode=mode))
 
 
 def pairs(valid, tr):

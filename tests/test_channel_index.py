@@ -26,6 +26,7 @@ import pytest
 
 import hostile
 import oracle
+import rxcheck
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "singlecarrier_amd", "csrc")
@@ -61,7 +62,7 @@ def _assert_symmetric(rx, name):
     np.testing.assert_array_equal(nbits, bits)
     for f in TRACE_FIELDS:
         np.testing.assert_array_equal(ntr[f], tr[f], err_msg=f)
-    assert not hostile.same_soft(ntr["soft"], tr["soft"]).any()
+    assert not rxcheck.same_soft(ntr["soft"], tr["soft"]).any()
 
 
 @pytest.mark.parametrize("name", ["clean", "eb4", "wave", "impaired"])

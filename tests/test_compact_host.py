@@ -11,11 +11,11 @@ import numpy as np
 import pytest
 
 import singlecarrier_amd as sc
+from compact_cases import SENT, filled, random_dense
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "singlecarrier_amd", "csrc")
 INC = os.path.join(ROOT, "include")
-SENT = 0xA5   # the fill of every output array before a call
 
 
 def restate(bits, valid, trace, soft, order):
@@ -32,26 +32,6 @@ def restate(bits, valid, trace, soft, order):
     w = ((bits[c, f] == 1).astype(np.uint64) << np.arange(62, dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
     groups = np.concatenate([[0], np.cumsum(per)]).astype(np.uint32)
     return c, f, w, trace[c, f], soft[c, f], groups
-
-
-def dense(rng, nch, nf, density, odd_bytes=False):
-    valid = (rng.random((nch, nf)) < density).astype(np.uint8)
-    valid *= rng.integers(1, 4, (nch, nf), dtype=np.uint8)   # any nonzero flag is valid
-    bits = rng.integers(0, 2, (nch, nf, 62), dtype=np.uint8)
-    if odd_bytes:
-        bits[rng.random(bits.shape) < 0.2] = 2
-        bits[rng.random(bits.shape) < 0.2] = 255
-    trace = rng.integers(-2**31, 2**31 - 1, (nch, nf, 4)).astype(np.int32)
-    soft = rng.standard_normal((nch, nf, 31, 2)).astype(np.float32)
-    return bits, valid, trace, soft
-
-
-def filled(cap, ngroups):
-    o = {"rec": np.zeros(cap, sc.REC_DTYPE), "trace": np.zeros((cap, 4), np.int32),
-         "soft": np.zeros((cap, 31, 2), np.float32), "groups": np.zeros(ngroups + 1, np.uint32)}
-    for a in o.values():
-        a.view(np.uint8)[...] = SENT
-    return o
 
 
 def check(bits, valid, trace, soft, order, cap):
@@ -80,7 +60,7 @@ def check(bits, valid, trace, soft, order, cap):
 @pytest.mark.parametrize("density", [0.0, 1.0, 0.2])
 def test_against_numpy(nch, nf, density, order):
     rng = np.random.default_rng(nch * 1000 + nf)
-    d = dense(rng, nch, nf, density, odd_bytes=True)
+    d = random_dense(rng, nch, nf, density, odd_bytes=True)
     count = check(*d, order, nch * nf)
     for cap in (0, count - 1, count, count + 5):
         if cap >= 0:
@@ -90,7 +70,7 @@ def test_against_numpy(nch, nf, density, order):
 @pytest.mark.parametrize("order", [sc.REC_BY_CHANNEL, sc.REC_BY_FRAME])
 def test_empty_leading_middle_and_trailing_groups(order):
     rng = np.random.default_rng(5)
-    bits, valid, trace, soft = dense(rng, 9, 9, 0.6)
+    bits, valid, trace, soft = random_dense(rng, 9, 9, 0.6)
     for k in (0, 1, 4, 5, 8):   # channels and frames with nothing valid
         valid[k, :] = 0
         valid[:, k] = 0
@@ -138,7 +118,7 @@ def test_pack_unpack_round_trip():
 
 def test_pure_count_and_optional_outputs():
     rng = np.random.default_rng(3)
-    bits, valid, trace, soft = dense(rng, 6, 5, 0.5)
+    bits, valid, trace, soft = random_dense(rng, 6, 5, 0.5)
     L = sc.lib()
     count = C.c_uint32(0)
     assert L.qpsk_compact_host(bits.ctypes.data, valid.ctypes.data, None, None, 6, 5, 0, 0, None, None, None, None,

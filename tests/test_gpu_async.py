@@ -36,7 +36,9 @@ import pytest
 
 import gpu_delay
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
+from rxcheck import KEYS
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -44,7 +46,6 @@ torch = pytest.importorskip("torch")
 NCH, NF = 96, 12
 CUTS = ((0, 1), (1, 4), (4, 12))         # calls of 1 + 3 + 8 frames
 SEED, DECOY = 41, 42
-KEYS = ("bits", "valid", "trace", "soft")
 ALAW_I = sc.IN_ALAW | sc.IN_INTERLEAVED
 ORDERS = [sc.REC_BY_CHANNEL, sc.REC_BY_FRAME]
 KNOBS = ("QPSK_SHAPE", "QPSK_WIDTH", "QPSK_HEADPASS")
@@ -58,15 +59,6 @@ PLANS = {"default": "1x8q16", "1x8w64": "1x8d64", "2x4d": "2x4d", "4x2": "4x2", 
 
 
 # ------------------------------------------------------------------ expected
-def _dense(x, mode=oracle.MODE_REF):
-    """The oracle's outputs of x as the dense arrays a receive call fills."""
-    bits, valid, tr = oracle.cpu_rx(x, trace=True, mode=mode)
-    trace = np.stack([tr[k] for k in ("max_index", "matches", "valid", "rx_timing")], -1).astype(np.int32)
-    soft = tr["soft"].copy()
-    soft[~valid.astype(bool)] = 0
-    return {"bits": bits, "valid": valid, "trace": trace, "soft": soft}
-
-
 def _cut(d, a, e, c0=0, c1=None):
     return {k: np.ascontiguousarray(d[k][c0:c1, a:e]) for k in KEYS}
 
@@ -86,10 +78,10 @@ def signal():
     oracle's outputs of the first; made once, never changed."""
     x = oracle.synth(SEED, NCH, NF, 1000.0)
     decoy = oracle.synth(DECOY, NCH, NF, 1000.0)
-    exp = {oracle.MODE_REF: _dense(x)}
+    exp = {oracle.MODE_REF: rxcheck.expected(x)}
     _pieces_depend(exp[oracle.MODE_REF], [(96, 96), (210, 288), (270, 768)])
     m = oracle.MODE_DEC752 | oracle.MODE_FFT_HUNT
-    exp[m] = _dense(x, m)
+    exp[m] = rxcheck.expected(x, m)
     _pieces_depend(exp[m])
     for a in (x, decoy):
         a.setflags(write=False)
@@ -102,7 +94,7 @@ def alaw(signal):
     oracle's outputs of what the codes decode to."""
     x, decoy, _ = signal
     codes = [sc.output_convert_host(a.reshape(NCH, -1), sc.OUT_ALAW | sc.OUT_INTERLEAVED) for a in (x, decoy)]
-    exp = _dense(sc.input_convert_host(codes[0], ALAW_I, NCH))
+    exp = rxcheck.expected(sc.input_convert_host(codes[0], ALAW_I, NCH))
     _pieces_depend(exp)
     return codes[0], codes[1], exp
 
@@ -407,7 +399,7 @@ def test_timing_pool_folds_with_calls_enqueued():
     64-slot event pool folds once, with calls still enqueued behind it"""
     nch, nf = 8, 70
     x = oracle.synth(43, nch, nf, 1000.0)
-    exp = _dense(x)
+    exp = rxcheck.expected(x)
     assert 0 < exp["valid"].sum() < nch * nf
     S = torch.cuda.Stream()
     # call n's arrays are block n: [nf][nch][1][...]
@@ -496,7 +488,7 @@ def test_reset_channels_with_a_call_in_flight(signal, D, monkeypatch):
     f.rx.reset_channels(c0, n)
     f.was_pending()   # the pending call's outputs are the continued stream's, on every channel
     got = f.last()
-    fresh = _dense(f.x[c0:c0 + n, 8:12])
+    fresh = rxcheck.expected(f.x[c0:c0 + n, 8:12])
     assert (fresh["valid"] != f.exp["valid"][c0:c0 + n, 8:12]).any()   # a reset is visible
     _same({k: got[k][c0:c0 + n] for k in KEYS}, fresh)
     _same({k: got[k][:c0] for k in KEYS}, _cut(f.exp, 8, 12, 0, c0))

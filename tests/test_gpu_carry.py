@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
 
 pytestmark = pytest.mark.gpu
@@ -28,23 +29,15 @@ pytestmark = pytest.mark.gpu
 FRAME = 1880
 HDR = 64
 TAIL = FRAME - 48
-KEYS = ("bits", "valid", "trace", "soft")
 
-# (QPSK_SHAPE, QPSK_WIDTH): pick_shape's choice for a small batch, and each forced shape
-SHAPES = [(None, None), ("4x2", None), ("2x4d", None), ("1x8", "64"), ("1x8", "32")]
+# (QPSK_SHAPE, QPSK_WIDTH): pick_shape's choice for a small batch, and each forced shape but W = 16
+SHAPES = [(None, None)] + rxcheck.ALL_SHAPES[:4]
 MODES = [sc.MODE_REFERENCE, sc.MODE_DEC752]
 _ORACLE_MODE = {sc.MODE_REFERENCE: oracle.MODE_REF, sc.MODE_DEC752: oracle.MODE_DEC752}
 _HEAD = {sc.MODE_REFERENCE: 1192, sc.MODE_DEC752: 1704}
 
 shapes = pytest.mark.parametrize("shape,width", SHAPES)
 modes = pytest.mark.parametrize("mode", MODES)
-
-
-def _force(monkeypatch, shape, width):
-    if shape:
-        monkeypatch.setenv("QPSK_SHAPE", shape)
-    if width:
-        monkeypatch.setenv("QPSK_WIDTH", width)
 
 
 @functools.lru_cache(maxsize=None)
@@ -61,27 +54,6 @@ def _expected(seed, nch, nf, ebn0, mode):
     return bits, valid, tr
 
 
-def _assert_same(out, bits, valid, tr):
-    np.testing.assert_array_equal(out["valid"], valid)
-    np.testing.assert_array_equal(out["bits"], bits)
-    t = out["trace"]
-    np.testing.assert_array_equal(t[..., 0], tr["max_index"])
-    np.testing.assert_array_equal(t[..., 1], tr["matches"])
-    np.testing.assert_array_equal(t[..., 3], tr["rx_timing"])
-    vm = valid.astype(bool)
-    np.testing.assert_array_equal(out["soft"][vm], tr["soft"][vm])
-    assert not out["soft"][~vm].any()
-
-
-def _split(rx, x, calls):
-    parts, a = [], 0
-    for f in calls:
-        parts.append(rx.demod(np.ascontiguousarray(x[:, a:a + f]), trace=True, soft=True))
-        a += f
-    assert a == x.shape[1]
-    return {k: np.concatenate([p[k] for p in parts], axis=1) for k in KEYS}
-
-
 def _history(rx, nch):
     snap = rx.state_save()
     return np.frombuffer(snap, np.int16, nch * 2 * FRAME, HDR).reshape(nch, 2, FRAME)
@@ -94,7 +66,7 @@ def test_history_bytes(nch, mode, shape, width, monkeypatch):
     """After every call of F = [3] and of F = [1, 1, 1, 2] the snapshot's whole
     history block equals the one built here from the inputs: the carried
     ranges hold the call's last frames and every other sample is zero."""
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     _check_history_bytes(nch, mode)
 
 
@@ -133,12 +105,12 @@ def _check_history_bytes(nch, mode):
 def test_split_calls(mode, shape, width, monkeypatch):
     """130 channels x 10 frames as calls of 1, 1, 2, 1 and 5 frames: bits,
     valid flags, trace and soft symbols equal the oracle's over the 10 frames."""
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     x = _input(410, 130, 10, 6.0)
     rx = sc.Receiver(130, mode=mode)
-    out = _split(rx, x, [1, 1, 2, 1, 5])
+    out = rxcheck.demod_in_calls(rx, x, [1, 1, 2, 1, 5])
     assert rx.frames == 10
-    _assert_same(out, *_expected(410, 130, 10, 6.0, mode))
+    rxcheck.assert_same(out, _expected(410, 130, 10, 6.0, mode))
     rx.close()
 
 
@@ -148,11 +120,11 @@ def test_pinned_small_calls(mode, shape, width, monkeypatch):
     """Host calls of at most 64 channel-frames read their input from the
     pinned staging block and write their outputs to it: 3 channels, five
     calls of 2 frames, equal to the oracle over the 10 frames."""
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     x = _input(420, 3, 10, 8.0)
     bits, valid, tr = _expected(420, 3, 10, 8.0, mode)
     assert valid.any() and not valid.all()   # data jobs ran, and not for every frame
     rx = sc.Receiver(3, mode=mode)
-    out = _split(rx, x, [2, 2, 2, 2, 2])
-    _assert_same(out, bits, valid, tr)
+    out = rxcheck.demod_in_calls(rx, x, [2, 2, 2, 2, 2])
+    rxcheck.assert_same(out, (bits, valid, tr))
     rx.close()

@@ -10,44 +10,20 @@ between a channel's index and its context's, on the quad and the lane backs, the
 pinned tiny-call path and a stream.
 
 Every expected value is the oracle's (oracle.cpu_rx) on the channel's own
-sub-stream from its latest start; every comparison is exact (bits, valid flags,
-the four trace columns, the soft symbols of valid frames bit for bit).
+sub-stream from its latest start; every comparison is tests/rxcheck.py's.
 """
 import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
 
 pytestmark = pytest.mark.gpu
 
 KS_FRAMES = 1057
-KEYS = ("bits", "valid", "trace", "soft")
 MODES = [sc.MODE_REFERENCE, sc.MODE_DEC752]
 MODE_IDS = ["reference", "dec752"]
-
-
-def _expect(x, mode):
-    """The oracle's outputs for x from a fresh start, in the layout of a
-    Receiver.demod(trace=True, soft=True) result."""
-    bits, valid, tr = oracle.cpu_rx(x, trace=True, mode=mode)
-    trace = np.stack([tr["max_index"], tr["matches"], tr["valid"], tr["rx_timing"]], axis=-1)
-    return {"bits": bits, "valid": valid, "trace": trace.astype(np.int32), "soft": np.ascontiguousarray(tr["soft"])}
-
-
-def _assert_same(got, exp, what=""):
-    np.testing.assert_array_equal(got["valid"], exp["valid"], err_msg=what)
-    np.testing.assert_array_equal(got["bits"], exp["bits"], err_msg=what)
-    if "trace" in got:
-        np.testing.assert_array_equal(got["trace"], exp["trace"], err_msg=what)
-    if "soft" in got:
-        vm = exp["valid"].astype(bool)
-        np.testing.assert_array_equal(got["soft"][vm].view(np.int32), exp["soft"][vm].view(np.int32), err_msg=what)
-        assert not got["soft"][~vm].any(), what
-
-
-def _cat(parts):
-    return {k: np.concatenate([p[k] for p in parts], axis=1) for k in parts[0]}
 
 
 def _sub(out, chans, frames=slice(None)):
@@ -90,7 +66,7 @@ def _come_and_go(nch, mode, calls, resets, seed):
             want = [int(edges[i + 1]) - max(s for s in starts[c] if s <= edges[i + 1]) for c in range(nch)]
             np.testing.assert_array_equal(own, np.asarray(want, np.uint64))
     rx.close()
-    got = _cat(parts)
+    got = {k: np.concatenate([p[k] for p in parts], axis=1) for k in rxcheck.KEYS}
     # channels with the same starts share an oracle run per segment
     groups = {}
     for c in range(nch):
@@ -99,14 +75,14 @@ def _come_and_go(nch, mode, calls, resets, seed):
     for st, chans in groups.items():
         seg = list(st) + [nf]
         for a, b in zip(seg[:-1], seg[1:]):
-            exp = _expect(x[chans, a:b], mode)
+            exp = rxcheck.expected(x[chans, a:b], mode)
             # each (range, segment) must be observed through a valid frame
             for ra, rb in ([(0, nch)] if st == (0,) else
                            [r for rs in resets for r in _clip(rs, nch)]):
                 inr = [k for k, c in enumerate(chans) if ra <= c < rb]
                 if inr:
                     assert exp["valid"][inr].any(), f"no valid frame: channels [{ra}, {rb}) frames [{a}, {b})"
-            _assert_same(_sub(got, chans, slice(a, b)), exp, f"starts {st}, frames [{a}, {b})")
+            rxcheck.assert_same(_sub(got, chans, slice(a, b)), exp, f"starts {st}, frames [{a}, {b})")
 
 
 # ------------------------------------------------------------- A. come and go
@@ -119,8 +95,7 @@ def test_channels_come_and_go(nch, shape, mode, monkeypatch):
     [1, 2) and the last channel at context frame 8 (even), 4 frames.  130
     channels run the quad backs; 4,500 would too (lane backs start above 8,192
     channels), so that case forces the 4x2 shape, whose backs are lane backs."""
-    if shape:
-        monkeypatch.setenv("QPSK_SHAPE", shape)
+    rxcheck.force_shape(monkeypatch, shape, None)
     _come_and_go(nch, mode, (3, 5, 4), [[(61, 131)], [(1, 2), (-1, 0)]], seed=11)
 
 
@@ -163,7 +138,7 @@ def test_keystream_wraps_inside_a_call():
     owns = [0, 1, 1056, 2113, 2**32 + 5]
     cut = [0, 13, 26, 39, 52, 64]
     x = oracle.synth(31, nch, k + more, 1000.0)
-    exp = _expect(x, sc.MODE_REFERENCE)
+    exp = rxcheck.expected(x, sc.MODE_REFERENCE)
     src = sc.Receiver(nch)
     src.demod(np.ascontiguousarray(x[:, :k]))
     snaps = [src.state_save(cut[i], cut[i + 1] - cut[i]) for i in range(len(owns))]
@@ -184,7 +159,7 @@ def test_keystream_wraps_inside_a_call():
         vm = e["valid"].astype(bool)
         assert vm.any(axis=0).all(), "a frame of the call is not observed in this group"
         e["bits"] = np.where(vm[..., None], e["bits"] ^ _keywords(k, more)[None] ^ _keywords(G, more)[None], 0)
-        _assert_same(_sub(got, ch), e, f"own index {G}")
+        rxcheck.assert_same(_sub(got, ch), e, f"own index {G}")
         # a snapshot carries the exact 64-bit index
         assert _frame_of(rx.state_save(cut[i], cut[i + 1] - cut[i])) == G + more
     rx.close()
@@ -230,14 +205,14 @@ def test_migration_continues_the_channels_stream(migration):
     want[3:43] = 7
     np.testing.assert_array_equal(m["own"], want)
     np.testing.assert_array_equal(m["own_after"], want + np.uint64(9))
-    ea = _expect(m["xa"][10:50, :16], sc.MODE_REFERENCE)
+    ea = rxcheck.expected(m["xa"][10:50, :16], sc.MODE_REFERENCE)
     assert ea["valid"][:, 7:].any(axis=1).sum() >= 30 and ea["valid"][:, 7:].any(axis=0).all()
-    _assert_same(_sub(m["rest"], slice(3, 43)), _sub(ea, slice(None), slice(7, 16)), "joined channels")
-    eb = _expect(m["xb"], sc.MODE_REFERENCE)
+    rxcheck.assert_same(_sub(m["rest"], slice(3, 43)), _sub(ea, slice(None), slice(7, 16)), "joined channels")
+    eb = rxcheck.expected(m["xb"], sc.MODE_REFERENCE)
     others = np.r_[0:3, 43:64]
     assert eb["valid"][others, 4:].any()
-    _assert_same(m["first"], _sub(eb, slice(None), slice(0, 4)), "B before the join")
-    _assert_same(_sub(m["rest"], others), _sub(eb, others, slice(4, 13)), "B's own channels")
+    rxcheck.assert_same(m["first"], _sub(eb, slice(None), slice(0, 4)), "B before the join")
+    rxcheck.assert_same(_sub(m["rest"], others), _sub(eb, others, slice(4, 13)), "B's own channels")
 
 
 def test_snapshots_of_joined_ranges(migration):
@@ -261,9 +236,9 @@ def test_snapshots_of_joined_ranges(migration):
     assert d.frames == 16 and (d.channel_frames() == 16).all()
     got = d.demod(np.ascontiguousarray(xa[10:50, 16:]), trace=True, soft=True)
     d.close()
-    e = _expect(xa[10:50], sc.MODE_REFERENCE)
+    e = rxcheck.expected(xa[10:50], sc.MODE_REFERENCE)
     assert e["valid"][:, 16:].any()
-    _assert_same(got, _sub(e, slice(None), slice(16, 18)), "loaded from a joined range's snapshot")
+    rxcheck.assert_same(got, _sub(e, slice(None), slice(16, 18)), "loaded from a joined range's snapshot")
 
 
 def test_snapshot_of_a_reset_range_and_load_after_it():
@@ -340,14 +315,14 @@ def test_stream_context_resets_channels_between_chunks():
     st.submit()
     b1, v1 = st.retrieve()
     st.close()
-    e = _expect(x, sc.MODE_REFERENCE)
-    _assert_same({"bits": b0, "valid": v0}, _sub(e, slice(None), slice(0, fpc)))
+    e = rxcheck.expected(x, sc.MODE_REFERENCE)
+    rxcheck.assert_same({"bits": b0, "valid": v0}, _sub(e, slice(None), slice(0, fpc)))
     others = np.r_[0:5, 15:nch]
     assert e["valid"][others, fpc:].any()
-    _assert_same({"bits": b1[others], "valid": v1[others]}, _sub(e, others, slice(fpc, None)))
-    fresh = _expect(x[5:15, fpc:], sc.MODE_REFERENCE)
+    rxcheck.assert_same({"bits": b1[others], "valid": v1[others]}, _sub(e, others, slice(fpc, None)))
+    fresh = rxcheck.expected(x[5:15, fpc:], sc.MODE_REFERENCE)
     assert fresh["valid"].any()
-    _assert_same({"bits": b1[5:15], "valid": v1[5:15]}, fresh)
+    rxcheck.assert_same({"bits": b1[5:15], "valid": v1[5:15]}, fresh)
 
 
 # ---------------------------------------------------------- F. stalled context
@@ -368,4 +343,4 @@ def test_stalled_context_refuses_a_channel_reset(monkeypatch):
     rx.reset_channels(0, 4)
     got = rx.demod(x, trace=True, soft=True)
     rx.close()
-    _assert_same(got, _expect(x, sc.MODE_REFERENCE))
+    rxcheck.assert_same(got, rxcheck.expected(x, sc.MODE_REFERENCE))

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import singlecarrier_amd as sc
-from test_compact_host import SENT, dense, filled
+from compact_cases import SENT, filled, random_dense
 
 pytestmark = pytest.mark.gpu
 
@@ -94,7 +94,7 @@ def run_case(dv, order, cap, rows=True, offs=(0, 0), groups=True):
 
 def make(seed, nch, nf, pattern):
     rng = np.random.default_rng(seed)
-    bits, valid, trace, soft = dense(rng, nch, nf, 0.2, odd_bytes=True)
+    bits, valid, trace, soft = random_dense(rng, nch, nf, 0.2, odd_bytes=True)
     if pattern == "all":
         valid[:] = 1
     elif pattern == "none":

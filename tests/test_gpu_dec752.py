@@ -7,7 +7,7 @@ input_frame.  It is NOT reference parity; its expected values come from
 oracle/_ref/libqpsk_ref752.so (the unmodified reference sources linked with the
 array padded, oracle/ref/dec752.ld) through the golden fixtures, and from the
 oracle restatement's dec752 mode, pinned to that build by tests/test_oracle.py.
-Every comparison is exact, soft symbols included.
+Every comparison with the oracle or an array golden is tests/rxcheck.py's.
 """
 import hashlib
 import json
@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
 
 pytestmark = pytest.mark.gpu
@@ -28,16 +29,7 @@ def _vs_oracle(x, **kw):
     rx = sc.Receiver(x.shape[0], mode=sc.MODE_DEC752)
     assert rx.mode == sc.MODE_DEC752
     out = rx.demod(x, trace=True, soft=True)
-    bits, valid, tr = oracle.cpu_rx(x, trace=True, mode=oracle.MODE_DEC752)
-    np.testing.assert_array_equal(out["valid"], valid)
-    np.testing.assert_array_equal(out["bits"], bits)
-    t = out["trace"]
-    np.testing.assert_array_equal(t[..., 0], tr["max_index"])
-    np.testing.assert_array_equal(t[..., 1], tr["matches"])
-    np.testing.assert_array_equal(t[..., 3], tr["rx_timing"])
-    vm = valid.astype(bool)
-    np.testing.assert_array_equal(out["soft"][vm], tr["soft"][vm])
-    assert not out["soft"][~vm].any()
+    rxcheck.assert_same(out, oracle.cpu_rx(x, trace=True, mode=oracle.MODE_DEC752))
     rx.close()
     return out
 
@@ -62,12 +54,8 @@ def test_synth_goldens(golden_dir, name):
     assert hashlib.sha256(x.tobytes()).hexdigest() == str(g["input_sha256"])
     rx = sc.Receiver(x.shape[0], mode=sc.MODE_DEC752)
     out = rx.demod(x, trace=True, soft=True)
-    np.testing.assert_array_equal(np.packbits(out["bits"], axis=-1), g["bits"])
-    np.testing.assert_array_equal(out["valid"], g["valid"])
-    np.testing.assert_array_equal(out["trace"][..., 0], g["max_index"])
-    np.testing.assert_array_equal(out["trace"][..., 1], g["matches"])
-    np.testing.assert_array_equal(out["trace"][..., 3], g["rx_timing"])
-    np.testing.assert_array_equal(out["soft"], g["soft"])
+    tr = {k: g[k] for k in ("max_index", "matches", "valid", "rx_timing", "soft")}   # the flag is kept once
+    rxcheck.assert_same(out, (np.unpackbits(g["bits"], axis=-1)[..., :oracle.NBITS], g["valid"], tr), name)
 
 
 @pytest.mark.parametrize("nch,ebn0", [(1, 1000.0), (65, 5.0), (2048, 1000.0), (1024, 2.0)])
@@ -91,7 +79,7 @@ def test_edge_inputs():
 
 @pytest.mark.parametrize("shape", ["4x2", "2x4d", "1x8"])
 def test_every_workgroup_shape(shape, monkeypatch):
-    monkeypatch.setenv("QPSK_SHAPE", shape)
+    rxcheck.force_shape(monkeypatch, shape, None)
     x = oracle.synth(62, 300, 12, 5.0)
     _vs_oracle(x)
 
@@ -111,10 +99,9 @@ def test_streaming_split_equals_one_call():
     x = oracle.synth(10, 130, 16, 6.0)
     whole = sc.Receiver(130, mode=sc.MODE_DEC752).demod(x, trace=True, soft=True)
     rx = sc.Receiver(130, mode=sc.MODE_DEC752)
-    parts = [rx.demod(np.ascontiguousarray(x[:, a:b]), trace=True, soft=True)
-             for a, b in ((0, 1), (1, 5), (5, 7), (7, 16))]
-    for k in ("bits", "valid", "trace", "soft"):
-        np.testing.assert_array_equal(np.concatenate([p[k] for p in parts], axis=1), whole[k])
+    parts = rxcheck.demod_in_calls(rx, x, (1, 4, 2, 9))
+    for k in rxcheck.KEYS:
+        np.testing.assert_array_equal(parts[k], whole[k])
 
 
 def test_modes_are_independent_contexts():
@@ -131,16 +118,12 @@ def test_modes_are_independent_contexts():
 
 def test_full_size_c3():
     """65536 channels x 32 frames in dec752 mode: bits, valid flags and the
-    rx_timing trace equal the oracle's for every channel."""
+    trace equal the oracle's for every channel."""
     nch, nf = 65536, 32
     x = oracle.synth(3, nch, nf)
     rx = sc.Receiver(nch, mode=sc.MODE_DEC752)
     out = rx.demod(x, trace=True)
-    bits, valid, tr = oracle.cpu_rx(x, trace=True, mode=oracle.MODE_DEC752)
-    np.testing.assert_array_equal(out["valid"], valid)
-    np.testing.assert_array_equal(out["bits"], bits)
-    np.testing.assert_array_equal(out["trace"][..., 3], tr["rx_timing"])
-    np.testing.assert_array_equal(out["trace"][..., 0], tr["max_index"])
+    rxcheck.assert_same(out, oracle.cpu_rx(x, trace=True, mode=oracle.MODE_DEC752))
 
 
 def test_c_driver_mode_flag(golden_dir, tmp_path):

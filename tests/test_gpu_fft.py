@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
 
 pytestmark = pytest.mark.gpu
@@ -94,7 +95,7 @@ def test_fft_device_writes_its_output_and_nothing_else(n, in_place):
 # ------------------------------------------------- the FFT-correlation hunt variant
 # QPSK_MODE_FFT_HUNT (flag): the receiver's hunt correlates through kiss_fft.
 # Expected values: the oracle restatement's same mode (its hunt pinned to the
-# reference's own fft() in tests/test_oracle.py).  Exact, soft symbols included.
+# reference's own fft() in tests/test_oracle.py), by tests/rxcheck.py's comparison.
 MODES = [sc.MODE_FFT_HUNT, sc.MODE_DEC752 | sc.MODE_FFT_HUNT]
 
 
@@ -102,13 +103,7 @@ def _vs_oracle(x, mode):
     rx = sc.Receiver(x.shape[0], mode=mode)
     assert rx.mode == mode
     out = rx.demod(x, trace=True, soft=True)
-    bits, valid, tr = oracle.cpu_rx(x, trace=True, mode=mode)
-    np.testing.assert_array_equal(out["trace"][..., 0], tr["max_index"])
-    np.testing.assert_array_equal(out["valid"], valid)
-    np.testing.assert_array_equal(out["bits"], bits)
-    np.testing.assert_array_equal(out["trace"][..., 3], tr["rx_timing"])
-    vm = valid.astype(bool)
-    np.testing.assert_array_equal(out["soft"][vm], tr["soft"][vm])
+    rxcheck.assert_same(out, oracle.cpu_rx(x, trace=True, mode=mode), f"mode {mode}")
     rx.close()
     return out
 
@@ -133,7 +128,7 @@ def test_fft_hunt_edge_inputs(mode):
 
 @pytest.mark.parametrize("shape", ["4x2", "2x4d", "1x8"])
 def test_fft_hunt_every_shape(shape, monkeypatch):
-    monkeypatch.setenv("QPSK_SHAPE", shape)
+    rxcheck.force_shape(monkeypatch, shape, None)
     _vs_oracle(oracle.synth(66, 300, 10, 3.0), sc.MODE_FFT_HUNT)
 
 
@@ -154,7 +149,4 @@ def test_fft_hunt_full_size():
     x = oracle.synth(3, nch, nf)
     rx = sc.Receiver(nch, mode=sc.MODE_FFT_HUNT)
     out = rx.demod(x, trace=True)
-    bits, valid, tr = oracle.cpu_rx(x, trace=True, mode=sc.MODE_FFT_HUNT)
-    np.testing.assert_array_equal(out["valid"], valid)
-    np.testing.assert_array_equal(out["bits"], bits)
-    np.testing.assert_array_equal(out["trace"][..., 0], tr["max_index"])
+    rxcheck.assert_same(out, oracle.cpu_rx(x, trace=True, mode=sc.MODE_FFT_HUNT))

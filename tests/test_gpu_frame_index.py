@@ -8,9 +8,8 @@ the stream; it is moved to 2^32 and beyond through a snapshot; one call holds
 more than 2^32 samples; and the kernel-time accounting (qpsk_rx_timing_*) is
 checked while its event pool folds.
 
-Every comparison is exact (bits, valid flags, the four trace columns, the soft
-symbols of valid frames bit for bit), against the oracle restatement
-(oracle/cpu_ref.c) of one continuous run from frame 0.
+Every comparison of a receive result is tests/rxcheck.py's, against the oracle
+restatement (oracle/cpu_ref.c) of one continuous run from frame 0.
 """
 import time
 
@@ -18,39 +17,13 @@ import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
 
 pytestmark = pytest.mark.gpu
 
 KS_FRAMES = 1057            # keystream period in frames
 G_PERIOD = 2 * KS_FRAMES    # period of everything the receive path takes from g
-KEYS = ("bits", "valid", "trace", "soft")
-
-
-def _assert_same(out, bits, valid, tr):
-    """tests/test_gpu_parity.py's comparison."""
-    np.testing.assert_array_equal(out["valid"], valid)
-    np.testing.assert_array_equal(out["bits"], bits)
-    if tr is not None and "trace" in out:
-        t = out["trace"]
-        np.testing.assert_array_equal(t[..., 0], tr["max_index"])
-        np.testing.assert_array_equal(t[..., 1], tr["matches"])
-        np.testing.assert_array_equal(t[..., 2], tr["valid"])
-        np.testing.assert_array_equal(t[..., 3], tr["rx_timing"])
-    if tr is not None and "soft" in out:
-        vm = valid.astype(bool)
-        np.testing.assert_array_equal(out["soft"][vm].view(np.int32), tr["soft"][vm].view(np.int32))
-        assert not out["soft"][~vm].any()
-
-
-def _in_calls(rx, x, calls):
-    """x fed to rx as consecutive calls of the given frame counts."""
-    assert sum(calls) == x.shape[1]
-    parts, a = [], 0
-    for n in calls:
-        parts.append(rx.demod(np.ascontiguousarray(x[:, a:a + n]), trace=True, soft=True))
-        a += n
-    return {k: np.concatenate([p[k] for p in parts], axis=1) for k in KEYS}
 
 
 # ------------------------------------------------- A. the period on every back
@@ -59,14 +32,11 @@ def long_stream():
     """130 clean channels x 1,070 frames and the oracle's outputs (read-only)."""
     x = oracle.synth(123, 130, 1070, 1000.0)
     bits, valid, tr = oracle.cpu_rx(x, trace=True)
-    for a in (x, bits, valid, tr):
-        a.setflags(write=False)
-    return x, bits, valid, tr
+    return rxcheck.frozen(x, bits, valid, tr)
 
 
 @pytest.mark.parametrize("calls", [(1050, 20), (1056, 1, 1, 12)], ids=["1050+20", "1056+1+1+12"])
-@pytest.mark.parametrize("shape,width", [("4x2", None), ("2x4d", None), ("1x8", "64"),
-                                         ("1x8", "32"), ("1x8", "16")])
+@pytest.mark.parametrize("shape,width", rxcheck.ALL_SHAPES)
 def test_keystream_period_on_every_back(shape, width, calls, long_stream, monkeypatch):
     """The descrambler word is reduced mod 1057 once in the lane back (train:
     4x2, 2x4 dual, 1x8 W = 64) and once in the quad back (qtrain: W = 32, 16).
@@ -74,14 +44,12 @@ def test_keystream_period_on_every_back(shape, width, calls, long_stream, monkey
     start at g = 1056, 1057 and 1058 (1056 + 1 + 1 + 12)."""
     x, bits, valid, tr = long_stream
     assert valid[:, KS_FRAMES:].any(axis=1).sum() >= 100   # channels seen past the period
-    monkeypatch.setenv("QPSK_SHAPE", shape)
-    if width:
-        monkeypatch.setenv("QPSK_WIDTH", width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     rx = sc.Receiver(x.shape[0])
-    out = _in_calls(rx, x, calls)
+    out = rxcheck.demod_in_calls(rx, x, calls)
     assert rx.frames == 1070
     rx.close()
-    _assert_same(out, bits, valid, tr)
+    rxcheck.assert_same(out, (bits, valid, tr), f"{shape}/{width}, calls {calls}")
 
 
 # ------------------------------------------- B. the drop-in and the stream
@@ -121,8 +89,8 @@ def test_stream_crosses_the_keystream_period(long_stream):
         got_b.append(b)
         got_v.append(v)
     st.close()
-    np.testing.assert_array_equal(np.concatenate(got_v, axis=1), valid[:nch])
-    np.testing.assert_array_equal(np.concatenate(got_b, axis=1), bits[:nch])
+    rxcheck.assert_same({"bits": np.concatenate(got_b, axis=1), "valid": np.concatenate(got_v, axis=1)},
+                        {"bits": bits[:nch], "valid": valid[:nch]})
 
 
 # ---------------------------------------- C. frame indices of 2^32 and beyond
@@ -161,8 +129,7 @@ def test_frame_index_past_32_bits(seed, k, G, shape, monkeypatch):
     x = oracle.synth(seed, nch, k + more, 1000.0)
     bits, valid, tr = oracle.cpu_rx(x, trace=True)
     assert valid[:, k:].sum(axis=0).min() >= 10   # every frame is observed through its bits
-    if shape:
-        monkeypatch.setenv("QPSK_SHAPE", shape)
+    rxcheck.force_shape(monkeypatch, shape, None)
     a = sc.Receiver(nch)
     a.demod(np.ascontiguousarray(x[:, :k]))
     snap = a.state_save()
@@ -174,7 +141,7 @@ def test_frame_index_past_32_bits(seed, k, G, shape, monkeypatch):
     assert b.frames == G + more
     snap2 = b.state_save()
     b.close()
-    _assert_same(rest, bits[:, k:], valid[:, k:], tr[:, k:])
+    rxcheck.assert_same(rest, (bits[:, k:], valid[:, k:], tr[:, k:]), f"G = {G}")
     assert _frame_of(snap2) == G + more
     c = sc.Receiver(nch)
     c.state_load(snap2)
@@ -197,9 +164,9 @@ def test_call_of_more_than_2_to_32_samples():
     if torch.cuda.mem_get_info()[0] < 16 * 2**30:
         pytest.skip("needs about 10 GB of device memory")
     u = oracle.synth(170, nu, F, 6.0)
-    bits, valid, tr = oracle.cpu_rx(u, trace=True)
+    exp = rxcheck.expected(u)
+    valid = exp["valid"]
     assert 0 < valid.sum() < valid.size
-    trace = np.stack([tr["max_index"], tr["matches"], tr["valid"], tr["rx_timing"]], axis=-1)
     idx = torch.arange(nch, device="cuda") % nu
     dx = torch.from_numpy(u).cuda()[idx]
     assert dx.is_contiguous() and dx.numel() > 2**32
@@ -212,13 +179,17 @@ def test_call_of_more_than_2_to_32_samples():
     rx.sync()
     assert rx.frames == F
     try:
-        assert torch.equal(dv, torch.from_numpy(valid).cuda()[idx])
-        assert torch.equal(db, torch.from_numpy(bits).cuda()[idx])
-        assert torch.equal(dt, torch.from_numpy(np.ascontiguousarray(trace)).cuda()[idx])
-        vm = torch.from_numpy(valid.astype(bool)).cuda()[idx]
-        es = torch.from_numpy(np.ascontiguousarray(tr["soft"])).cuda()[idx]
-        assert torch.equal(ds[vm].view(torch.int32), es[vm].view(torch.int32))
-        assert not ds[~vm].any()
+        # 2.3 million channel-frames, compared where they are.  The rules are rxcheck.differences':
+        # exp's soft symbols hold no NaN and are zero on invalid frames, so every bit is compared
+        assert not np.isnan(exp["soft"]).any()
+        for k, got in zip(rxcheck.KEYS, (db, dv, dt, ds.view(torch.int32))):
+            want = torch.from_numpy(np.array(exp[k]).view(np.int32 if k == "soft" else exp[k].dtype)).cuda()[idx]
+            assert got.shape == want.shape and got.dtype == want.dtype, k
+            if not torch.equal(got, want):
+                bad = (got != want).reshape(nch, F, -1).any(-1)
+                raise AssertionError(f"{k} differs on {int(bad.sum())} channel-frames, "
+                                     f"first at (channel, frame) {tuple(bad.nonzero()[0].tolist())}")
+            del want
     finally:
         rx.close()
         del dx, db, dv, dt, ds, idx
@@ -238,7 +209,7 @@ def test_kernel_time_accounting_folds_its_event_pool():
     rx.timing(True)
     parts = []
     t0 = time.perf_counter()
-    for n in range(timed):
+    for n in range(timed):   # written out: nothing but the calls inside the host's span
         parts.append(rx.demod(np.ascontiguousarray(x[:, n:n + 1]), trace=True, soft=True))
     host_ms = (time.perf_counter() - t0) * 1e3
     ms_rx, ms_data, frames = rx.collect_timing_split()
@@ -248,10 +219,9 @@ def test_kernel_time_accounting_folds_its_event_pool():
     assert ms_rx + ms_data <= host_ms
     assert rx.collect_timing_split() == (0.0, 0.0, 0)
     rx.timing(False)
-    for n in range(timed, timed + untimed):
-        parts.append(rx.demod(np.ascontiguousarray(x[:, n:n + 1]), trace=True, soft=True))
+    parts.append(rxcheck.demod_in_calls(rx, x[:, timed:], [1] * untimed))
     assert rx.collect_timing_split() == (0.0, 0.0, 0)
     assert rx.collect_timing() == (0.0, 0)
     rx.close()
-    out = {k: np.concatenate([p[k] for p in parts], axis=1) for k in KEYS}
-    _assert_same(out, bits, valid, tr)
+    out = {k: np.concatenate([p[k] for p in parts], axis=1) for k in rxcheck.KEYS}
+    rxcheck.assert_same(out, (bits, valid, tr))

@@ -4,9 +4,8 @@ Its fronts prefetch frames n >= 2 of a call from one scalar base (the three
 source frames are consecutive rows of the input: prefetch_rows; frames 0 and 1
 read the carried history and keep the general path), and the split FIR derives
 its per-lane LDS addresses from the wave-uniform rx_timing.  Every case forces
-QPSK_SHAPE=4x2 and compares bits, valid flags, max_index, matches, rx_timing
-and the soft symbols bit for bit with the oracle (oracle/cpu_ref.c),
-tests/test_gpu_carry.py's comparison.
+QPSK_SHAPE=4x2 and compares every output with the oracle's (oracle/cpu_ref.c)
+by tests/rxcheck.py's comparison.
 
 Which paths a corpus reaches is asserted on the oracle's trace first, so that
 no case can pass on an input that never takes them.  On rx_timing: a fresh
@@ -16,12 +15,15 @@ the only one at which the FIR reads the input's first item, M[0..127]) is
 therefore the incoming rx_timing of a stream's first frame and of no other,
 which is frame 0 of a context's first call, on the general path.
 """
+import functools
+
 import numpy as np
 import pytest
 
+import oracle
+import rxcheck
 import singlecarrier_amd as sc
 import timing
-from test_gpu_carry import _assert_same, _expected, _input, _split
 
 pytestmark = pytest.mark.gpu
 
@@ -29,9 +31,16 @@ SPLIT_MI = 93        # qpsk_rx_front.h kSplitMi: the split FIR's tail runs from 
 NOISY = (23, 300, 6, 5.0)   # seed, channels (not a multiple of 32, 64 or 256), frames, Eb/N0
 
 
+@functools.lru_cache(maxsize=None)
+def _noisy():
+    """The NOISY input and the oracle's (bits, valid, trace) for it, made once, read-only."""
+    x = sc.synth(*NOISY)
+    return rxcheck.frozen(x)[0], rxcheck.frozen(*oracle.cpu_rx(x, trace=True))
+
+
 @pytest.fixture(autouse=True)
 def _shape(monkeypatch):
-    monkeypatch.setenv("QPSK_SHAPE", "4x2")
+    rxcheck.force_shape(monkeypatch, "4x2", None)
 
 
 def _paths(tr, calls):
@@ -52,10 +61,10 @@ def _paths(tr, calls):
 
 def _run(x, exp, calls):
     rx = sc.Receiver(x.shape[0])
-    out = _split(rx, x, list(calls))
+    out = rxcheck.demod_in_calls(rx, x, calls)
     assert rx.frames == x.shape[1]
     rx.close()
-    _assert_same(out, *exp)
+    rxcheck.assert_same(out, exp, f"calls {calls}")
 
 
 @pytest.mark.parametrize("calls", [(6,), (1, 2, 3), (3, 1, 2)])
@@ -63,7 +72,7 @@ def test_noisy_300_channels(calls):
     """300 channels x 6 frames in one call, and in calls of 1, 2 and 3 frames
     chained on one context: a call's frames 0 and 1 read the history the calls
     before it left, its frame 2 takes the one-base path."""
-    x, exp = _input(*NOISY), _expected(*NOISY, sc.MODE_REFERENCE)
+    x, exp = _noisy()
     _paths(exp[2], calls)
     _run(x, exp, calls)
 
@@ -100,4 +109,4 @@ def test_impulses_exact_ties(calls):
 def test_forced_exact(monkeypatch):
     """Every frame through the EXACT = true recomputation (QPSK_FORCE_EXACT)."""
     monkeypatch.setenv("QPSK_FORCE_EXACT", "1")
-    _run(_input(*NOISY), _expected(*NOISY, sc.MODE_REFERENCE), (6,))
+    _run(*_noisy(), (6,))

@@ -6,24 +6,18 @@ must a create that fails half way.  Run with -m gpu.
 
 All of it on 96 channels x 2 frames: one and a half groups, the raggedest small
 batch."""
-import ctypes as C
 import gc
 
 import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
 
 pytestmark = pytest.mark.gpu
 
 NCH, NF = 96, 2
-
-
-def _live():
-    f = sc.lib().qpsk_hip_live_handles
-    f.restype, f.argtypes = C.c_long, []
-    return int(f())
 
 
 @pytest.fixture(scope="module")
@@ -33,9 +27,9 @@ def x():
 
 @pytest.fixture(scope="module")
 def expected(x):
-    """mode -> (bits, valid, trace) of the oracle, and one packet per channel
-    through the host transmitter; computed once"""
-    e = {m: oracle.cpu_rx(x, trace=True, mode=m) for m in (0, 3)}
+    """mode -> the oracle's dense outputs, and one packet per channel through
+    the host transmitter; computed once"""
+    e = {m: rxcheck.expected(x, m) for m in (0, 3)}
     e["payload"] = np.random.default_rng(5).integers(0, 2, (NCH, 1, 8, sc.NBITS), dtype=np.uint8)
     e["tx"] = sc.tx_batch_host(e["payload"])
     e["fft_in"] = (np.arange(256) % 7 - 3).astype(np.complex64)
@@ -43,53 +37,44 @@ def expected(x):
     return e
 
 
-def _assert_oracle(out, exp):
-    bits, valid, tr = exp
-    np.testing.assert_array_equal(out["valid"], valid)
-    np.testing.assert_array_equal(out["bits"], bits)
-    for k, name in enumerate(("max_index", "matches", "valid", "rx_timing")):
-        np.testing.assert_array_equal(out["trace"][..., k], tr[name])
-
-
 def _round(x, expected, monkeypatch, base):
     """One of everything, used once and closed; the counter is back at `base`
     after every close."""
     for mode in (0, 3):
         rx = sc.Receiver(NCH, mode=mode)
-        assert _live() > base
-        _assert_oracle(rx.demod(x, trace=True, soft=True), expected[mode])   # staging + job queue
+        assert rxcheck.live_handles() > base
+        rxcheck.assert_same(rx.demod(x, trace=True, soft=True), expected[mode])   # staging + job queue
         rx.close()
-        assert _live() == base, f"Receiver(mode={mode})"
+        assert rxcheck.live_handles() == base, f"Receiver(mode={mode})"
     monkeypatch.setenv("QPSK_HEADPASS", "1")
     rx = sc.Receiver(NCH)
     monkeypatch.delenv("QPSK_HEADPASS")
-    _assert_oracle(rx.demod(x, trace=True), expected[0])                     # + the head pre-pass buffer
+    rxcheck.assert_same(rx.demod(x, trace=True), expected[0])                     # + the head pre-pass buffer
     rx.close()
-    assert _live() == base, "Receiver under QPSK_HEADPASS=1"
+    assert rxcheck.live_handles() == base, "Receiver under QPSK_HEADPASS=1"
     st = sc.Stream(NCH, NF, nslot=3)
     st.acquire()[:] = x
     st.submit()
     bits, valid = st.retrieve()
-    np.testing.assert_array_equal(valid, expected[0][1])
-    np.testing.assert_array_equal(bits, expected[0][0])
+    rxcheck.assert_same({"bits": bits, "valid": valid}, expected[0], "Stream")
     st.close()
-    assert _live() == base, "Stream"
+    assert rxcheck.live_handles() == base, "Stream"
     tx = sc.Transmitter(NCH)
     np.testing.assert_array_equal(tx.modulate(expected["payload"]), expected["tx"])
     tx.close()
-    assert _live() == base, "Transmitter"
+    assert rxcheck.live_handles() == base, "Transmitter"
     plan = sc.FftPlan(256)
     np.testing.assert_array_equal(plan(expected["fft_in"]).view(np.uint32), expected["fft"].view(np.uint32))
     plan.close()
-    assert _live() == base, "FftPlan"
+    assert rxcheck.live_handles() == base, "FftPlan"
 
 
 def test_nothing_is_left_alive(x, expected, monkeypatch):
     gc.collect()   # receivers earlier tests dropped without close()
-    base = _live()
+    base = rxcheck.live_handles()
     for _ in range(1 + 10):
         _round(x, expected, monkeypatch, base)
-    assert _live() == base
+    assert rxcheck.live_handles() == base
 
 
 def test_failed_create_cleans_up_behind_itself(x, expected):
@@ -102,19 +87,19 @@ def test_failed_create_cleans_up_behind_itself(x, expected):
     with the create's own code.  That call is made here all the same, so the
     stale error ends in this test, and the receiver after it is checked."""
     gc.collect()
-    base = _live()
+    base = rxcheck.live_handles()
     with pytest.raises(sc.QpskError) as ei:
         sc.Receiver(1 << 27)
     assert ei.value.code != 0
-    assert _live() == base
+    assert rxcheck.live_handles() == base
     rx = sc.Receiver(NCH)
     try:
         rx.demod(x, trace=True)
     except sc.QpskError as e:
         assert e.code == ei.value.code
     rx.close()
-    assert _live() == base
+    assert rxcheck.live_handles() == base
     rx = sc.Receiver(NCH)
-    _assert_oracle(rx.demod(x, trace=True), expected[0])
+    rxcheck.assert_same(rx.demod(x, trace=True), expected[0])
     rx.close()
-    assert _live() == base
+    assert rxcheck.live_handles() == base

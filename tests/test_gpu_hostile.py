@@ -5,9 +5,9 @@ products take gcc's Annex G recovery.  The expected values are the oracle's
 (oracle/cpu_ref.c), pinned to the unmodified reference on this very corpus by
 tests/test_oracle.py.
 
-Comparison: valid, bits and the four trace columns exact; soft symbols of valid
-frames exact for finite values and infinities, NaN compared as NaN only (the
-GPU's NaN payloads and signs need not be x86's); soft zero on invalid frames.
+Comparison: tests/rxcheck.py's with nan_as_class=True: soft symbols of valid
+frames bit for bit for finite values and infinities, NaN compared as NaN only
+(the GPU's NaN payloads and signs need not be x86's).
 """
 import os
 
@@ -16,55 +16,23 @@ import pytest
 
 import hostile
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ("bits", "valid", "trace", "soft")
-
-
-def _first(mask):
-    """(count, first channel-frame) of a [nch][nframes][...] mask"""
-    m = mask.reshape(mask.shape[0], mask.shape[1], -1).any(-1)
-    cf = np.argwhere(m)
-    return int(m.sum()), (tuple(int(v) for v in cf[0]) if len(cf) else None)
-
-
-def _assert_same(out, exp, what=""):
-    """Every output against the oracle's; the message names each differing
-    output with its count and first differing (channel, frame)."""
-    bits, valid, tr = exp
-    vm = valid.astype(bool)
-    bad = {}
-    checks = [("valid", out["valid"] != valid), ("bits", out["bits"] != bits)]
-    if "trace" in out:
-        for col, k in enumerate(("max_index", "matches", "valid", "rx_timing")):
-            checks.append(("trace." + k, out["trace"][..., col] != tr[k]))
-    if "soft" in out:
-        checks.append(("soft(valid)", hostile.same_soft(out["soft"], tr["soft"]) & vm[..., None, None]))
-        checks.append(("soft(invalid) != 0", (out["soft"].view(np.uint32) != 0) & ~vm[..., None, None]))
-    for name, mask in checks:
-        n, at = _first(mask)
-        if n:
-            bad[name] = (n, at)
-    for name, (n, at) in bad.items():
-        print(f"{what}: {name} differs on {n} channel-frames, first at (channel, frame) {at}")
-    assert not bad, f"{what}: {bad}"
-
 
 def _demod(x, mode=sc.MODE_REFERENCE, cuts=None):
+    """x through a fresh context, as calls that end at the frames `cuts` and at the last."""
     rx = sc.Receiver(x.shape[0], mode=mode)
-    parts, a = [], 0
-    for b in (cuts or []) + [x.shape[1]]:
-        parts.append(rx.demod(np.ascontiguousarray(x[:, a:b]), trace=True, soft=True))
-        a = b
+    out = rxcheck.demod_in_calls(rx, x, np.diff([0] + (cuts or []) + [x.shape[1]]))
     rx.close()
-    return {k: np.concatenate([p[k] for p in parts], axis=1) for k in KEYS}
+    return out
 
 
 def _run(name="wave", mode=sc.MODE_REFERENCE, cuts=None, what=""):
-    _assert_same(_demod(hostile.group(name), mode, cuts), hostile.expected(name, mode),
-                 what or name)
+    rxcheck.assert_same(_demod(hostile.group(name), mode, cuts), hostile.expected(name, mode),
+                        what or name, nan_as_class=True)
 
 
 def test_device_product_equals_the_oracles():
@@ -88,7 +56,7 @@ def test_device_product_equals_the_oracles():
     assert lib.cmul_check(ops.ctypes.data, got.ctypes.data, len(ops)) == 0
     conj = ops * np.array([1, 1, 1, -1], np.float32)
     exp = np.concatenate([oracle.cmul(ops), oracle.cmul(conj)], axis=1)
-    bad = hostile.same_soft(got, exp).any(1)
+    bad = rxcheck.same_soft(got, exp).any(1)
     assert not bad.any(), (int(bad.sum()), ops[bad][0], got[bad][0], exp[bad][0])
     assert np.isinf(exp).any() and np.isnan(exp).any()
 
@@ -107,15 +75,14 @@ def test_corpus_holds_non_finite_valid_frames():
 def test_corpus_every_shape(shape, monkeypatch):
     """The 160 wave channels x 12 frames at the shape the batch size selects
     (one group per workgroup, quad backs) and with each rx_kernel shape forced."""
-    if shape:
-        monkeypatch.setenv("QPSK_SHAPE", shape)
+    rxcheck.force_shape(monkeypatch, shape, None)
     _run(what=f"shape {shape}")
 
 
 @pytest.mark.parametrize("width", ["16", "32", "64"])
 def test_corpus_group_widths(width, monkeypatch):
     """Quad backs (W = 16, 32) and lane backs (W = 64) of the dual-chain kernel."""
-    monkeypatch.setenv("QPSK_WIDTH", width)
+    rxcheck.force_shape(monkeypatch, None, width)
     _run(what=f"width {width}")
 
 
@@ -142,7 +109,7 @@ def test_tiny_host_call():
     table's first 8 rows, sensitive inside their first 4 frames."""
     x = np.ascontiguousarray(hostile.group("wave")[:8, :4])
     exp = tuple(a[:8, :4] for a in hostile.expected("wave"))
-    _assert_same(_demod(x), exp, "tiny call")
+    rxcheck.assert_same(_demod(x), exp, "tiny call", nan_as_class=True)
 
 
 def test_rx_frame_surface_against_the_golden(golden_dir):
@@ -182,8 +149,8 @@ def test_stream_chunks():
     while st.pending:
         got.append(st.retrieve())
     st.close()
-    np.testing.assert_array_equal(np.concatenate([v for _, v in got], axis=1), valid)
-    np.testing.assert_array_equal(np.concatenate([b for b, _ in got], axis=1), bits)
+    rxcheck.assert_same({"bits": np.concatenate([b for b, _ in got], axis=1),
+                         "valid": np.concatenate([v for _, v in got], axis=1)}, {"bits": bits, "valid": valid})
 
 
 @pytest.mark.parametrize("mode", [sc.MODE_DEC752, sc.MODE_FFT_HUNT, sc.MODE_DEC752 | sc.MODE_FFT_HUNT])
@@ -195,6 +162,5 @@ def test_corpus_receiver_modes(mode):
 def test_impaired_group_every_shape(shape, monkeypatch):
     """The finite side: echoes, clipping gains, DC offsets and a level step on
     the modem's own signal (|soft| up to 1e10, match counts at the threshold)."""
-    if shape:
-        monkeypatch.setenv("QPSK_SHAPE", shape)
+    rxcheck.force_shape(monkeypatch, shape, None)
     _run("impaired", what=f"impaired, shape {shape}")

@@ -12,7 +12,8 @@ import pytest
 
 import oracle
 import singlecarrier_amd as sc
-from test_input_host import TABLES, expand
+from g711 import TABLES, expand
+from rxcheck import assert_same, expected, live_handles
 
 pytestmark = pytest.mark.gpu
 
@@ -207,7 +208,8 @@ class Case:
         self.enc, self.nch, self.nframes, self.mode = enc, nch, nframes, mode
         self.codes = _encode(x.reshape(nch, -1).astype(np.int64), enc)        # [nch][T]
         self.y = expand(self.codes, enc).reshape(nch, nframes, sc.FRAME_SIZE)
-        self.bits, self.valid, self.tr = oracle.cpu_rx(self.y, trace=True, mode=mode)
+        self.exp = expected(self.y, mode)
+        self.bits, self.valid = self.exp["bits"], self.exp["valid"]
 
     def block(self, layout, ld=None):
         if layout == sc.IN_PLANAR:
@@ -217,12 +219,7 @@ class Case:
         return wide[:, :self.nch]
 
     def check(self, out):
-        np.testing.assert_array_equal(out["valid"], self.valid)
-        np.testing.assert_array_equal(out["bits"], self.bits)
-        for k, name in enumerate(("max_index", "matches", "valid", "rx_timing")):
-            np.testing.assert_array_equal(out["trace"][..., k], self.tr[name])
-        vm = self.valid.astype(bool)
-        assert (out["soft"][vm].view(np.uint32) == self.tr["soft"][vm].view(np.uint32)).all()
+        assert_same(out, self.exp)
 
 
 @pytest.fixture(scope="module")
@@ -328,12 +325,6 @@ def test_demod_device_fmt_on_a_torch_stream(cases, enc, layout):
 
 
 # ------------------------------------------------------------------ streams
-def _live():
-    f = sc.lib().qpsk_hip_live_handles
-    f.restype, f.argtypes = C.c_long, []
-    return int(f())
-
-
 def test_a_stream_of_interleaved_alaw_equals_the_batch(cases):
     case = cases[sc.IN_ALAW]
     fmt = sc.IN_ALAW | sc.IN_INTERLEAVED
@@ -350,8 +341,7 @@ def test_a_stream_of_interleaved_alaw_equals_the_batch(cases):
         st.submit()
     got = [st.retrieve() for _ in range(2)]
     st.close()
-    np.testing.assert_array_equal(np.concatenate([g[1] for g in got], axis=1), case.valid)
-    np.testing.assert_array_equal(np.concatenate([g[0] for g in got], axis=1), case.bits)
+    case.check({k: np.concatenate([g[i] for g in got], axis=1) for i, k in enumerate(("bits", "valid"))})
 
 
 def test_a_default_stream_is_unaffected(cases):
@@ -366,8 +356,7 @@ def test_a_default_stream_is_unaffected(cases):
     raw = st.acquire_raw()
     assert raw.shape == (96, 4 * sc.FRAME_SIZE) and raw.dtype == np.int16
     st.close()
-    np.testing.assert_array_equal(np.concatenate([g[1] for g in got], axis=1), case.valid)
-    np.testing.assert_array_equal(np.concatenate([g[0] for g in got], axis=1), case.bits)
+    case.check({k: np.concatenate([g[i] for g in got], axis=1) for i, k in enumerate(("bits", "valid"))})
 
 
 def test_handles_are_back_at_their_base(cases):
@@ -377,7 +366,7 @@ def test_handles_are_back_at_their_base(cases):
     import torch
     case = cases[sc.IN_ALAW]
     gc.collect()
-    base = _live()
+    base = live_handles()
     rx = sc.Receiver(96)
     rx.demod_fmt(case.codes, sc.IN_ALAW)
     x = torch.from_numpy(np.ascontiguousarray(case.codes.T)).cuda()
@@ -385,15 +374,15 @@ def test_handles_are_back_at_their_base(cases):
     valid = torch.zeros((96, 8), dtype=torch.uint8, device="cuda")
     rx.demod_device_fmt(x, sc.IN_ALAW | sc.IN_INTERLEAVED, bits, valid)
     rx.sync()
-    assert _live() > base
+    assert live_handles() > base
     rx.close()
-    assert _live() == base, "Receiver"
+    assert live_handles() == base, "Receiver"
     st = sc.Stream(96, 8, nslot=2, fmt=sc.IN_ALAW)
     st.acquire_raw()[...] = case.codes
     st.submit()
     np.testing.assert_array_equal(st.retrieve()[1], case.valid)
     st.close()
-    assert _live() == base, "Stream"
+    assert live_handles() == base, "Stream"
 
 
 # ------------------------------------------------------------------ the C example

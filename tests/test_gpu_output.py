@@ -12,8 +12,8 @@ import pytest
 
 import oracle
 import singlecarrier_amd as sc
-from test_input_host import TABLES
-from test_output_host import compress
+from g711 import TABLES, compress
+from rxcheck import assert_same, live_handles
 
 pytestmark = pytest.mark.gpu
 
@@ -422,7 +422,6 @@ def test_loopback_through_an_interleaved_trunk_of_codes(loop, enc):
     8 x 1880 rows go to demod_device_fmt as they are"""
     import torch
     bits, exp = loop
-    want_bits, want_valid, tr = exp[enc]
     fmt = enc | sc.OUT_INTERLEAVED
     tx, rx = sc.Transmitter(24, gap=903), sc.Receiver(24)
     trunk = torch.zeros((6 * 2783, 24), dtype=torch.uint8, device="cuda")
@@ -434,23 +433,12 @@ def test_loopback_through_an_interleaved_trunk_of_codes(loop, enc):
     rx.demod_device_fmt(trunk[:8 * 1880], fmt, out["bits"], out["valid"], out["trace"], out["soft"])
     rx.sync()
     out = {k: v.cpu().numpy() for k, v in out.items()}
-    np.testing.assert_array_equal(out["valid"], want_valid)
-    np.testing.assert_array_equal(out["bits"], want_bits)
-    for k, name in enumerate(("max_index", "matches", "valid", "rx_timing")):
-        np.testing.assert_array_equal(out["trace"][..., k], tr[name])
-    vm = want_valid.astype(bool)
-    assert (out["soft"][vm].view(np.uint32) == tr["soft"][vm].view(np.uint32)).all()
+    assert_same(out, exp[enc], hex(fmt))
     tx.close()
     rx.close()
 
 
 # ------------------------------------------------------------------ other contexts
-def _live():
-    f = sc.lib().qpsk_hip_live_handles
-    f.restype, f.argtypes = C.c_long, []
-    return int(f())
-
-
 def test_two_contexts_on_two_streams_in_different_formats():
     import torch
     nch, gap, N = 70, 1, 3 * 1881
@@ -480,7 +468,7 @@ def test_default_format_calls_are_unaffected_and_handles_return():
     bits = np.random.default_rng(14).integers(0, 2, (nch, 3, 8, 62), dtype=np.uint8)
     want = sc.tx_batch_host(bits, gap=gap)
     gc.collect()
-    base = _live()
+    base = live_handles()
     tx = sc.Transmitter(nch, gap=gap)
     first = tx.modulate_fmt(bits[:, :1], sc.OUT_ALAW | sc.OUT_INTERLEAVED)
     np.testing.assert_array_equal(first, compress(want[:, :2783], sc.OUT_ALAW).T)
@@ -494,9 +482,9 @@ def test_default_format_calls_are_unaffected_and_handles_return():
     tx.reset()
     tx.modulate_device_fmt(torch.from_numpy(np.ascontiguousarray(bits[:, :1])).cuda(), codes, sc.OUT_ULAW)
     tx.sync()
-    assert _live() > base
+    assert live_handles() > base
     tx.close()
-    assert _live() == base
+    assert live_handles() == base
 
 
 # ------------------------------------------------------------------ the C examples

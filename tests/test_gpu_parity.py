@@ -1,10 +1,13 @@
 """Parity of the MI355X receive path with the reference (run with -m gpu).
 
-Every comparison is exact: bits, valid flags, max_index/matches/rx_timing
-traces and the soft I/Q symbols of valid frames are compared bit for bit
-(the north_star's 1e-5 RMS soft-symbol tolerance is therefore
-met with zero error).  Expected values come from the golden fixtures made by
-the unmodified reference (tests/golden/make_golden.py) and, at larger sizes,
+Every comparison with the oracle or an array golden is tests/rxcheck.py's:
+bits, valid flags, the four trace columns and the soft I/Q symbols of valid
+frames bit for bit (the north_star's 1e-5 RMS soft-symbol
+tolerance is therefore met with zero error).  The sample-file cases compare
+with md5 sums and JSON records, and the stage golden's soft symbols by value.
+Two results of the GPU (split calls, snapshots) are compared with each other
+by value.  Expected values come from the golden fixtures made by the
+unmodified reference (tests/golden/make_golden.py) and, at larger sizes,
 from the oracle restatement (oracle/cpu_ref.c), itself pinned to the reference
 by tests/test_oracle.py.
 """
@@ -16,6 +19,7 @@ import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
 
 pytestmark = pytest.mark.gpu
@@ -27,26 +31,10 @@ def _sample(golden_dir):
     return sc.read_raw(os.path.join(golden_dir, "preamble_qpsk_8k.raw"))
 
 
-def _assert_same(out, bits, valid, tr):
-    np.testing.assert_array_equal(out["valid"], valid)
-    np.testing.assert_array_equal(out["bits"], bits)
-    if tr is not None and "trace" in out:
-        t = out["trace"]
-        np.testing.assert_array_equal(t[..., 0], tr["max_index"])
-        np.testing.assert_array_equal(t[..., 1], tr["matches"])
-        np.testing.assert_array_equal(t[..., 2], tr["valid"])
-        np.testing.assert_array_equal(t[..., 3], tr["rx_timing"])
-    if tr is not None and "soft" in out:
-        vm = valid.astype(bool)
-        np.testing.assert_array_equal(out["soft"][vm], tr["soft"][vm])
-        assert not out["soft"][~vm].any()
-
-
 def _vs_oracle(x, **kw):
     rx = sc.Receiver(x.shape[0])
     out = rx.demod(x, trace=True, soft=True)
-    bits, valid, tr = oracle.cpu_rx(x, trace=True)
-    _assert_same(out, bits, valid, tr)
+    rxcheck.assert_same(out, oracle.cpu_rx(x, trace=True))
     rx.close()
     return out
 
@@ -85,12 +73,8 @@ def test_synth_goldens(golden_dir, name):
     assert hashlib.sha256(x.tobytes()).hexdigest() == str(g["input_sha256"])
     rx = sc.Receiver(x.shape[0])
     out = rx.demod(x, trace=True, soft=True)
-    np.testing.assert_array_equal(np.packbits(out["bits"], axis=-1), g["bits"])
-    np.testing.assert_array_equal(out["valid"], g["valid"])
-    np.testing.assert_array_equal(out["trace"][..., 0], g["max_index"])
-    np.testing.assert_array_equal(out["trace"][..., 1], g["matches"])
-    np.testing.assert_array_equal(out["trace"][..., 3], g["rx_timing"])
-    np.testing.assert_array_equal(out["soft"], g["soft"])
+    tr = {k: g[k] for k in ("max_index", "matches", "valid", "rx_timing", "soft")}   # the flag is kept once
+    rxcheck.assert_same(out, (np.unpackbits(g["bits"], axis=-1)[..., :oracle.NBITS], g["valid"], tr), name)
 
 
 def test_c2_4096_channels():
@@ -129,8 +113,7 @@ def test_low_amplitude_streams(shift, shape, monkeypatch):
     forced 4x2 / 2x4d.  No window here has two lags at exactly the maximum
     (replayed on the oracle's dec with tests/timing.py hunt_classes): exact
     ties are the impulses of tests/test_gpu_timing.py."""
-    if shape:
-        monkeypatch.setenv("QPSK_SHAPE", shape)
+    rxcheck.force_shape(monkeypatch, shape, None)
     x = (oracle.synth(31 + shift, 256, 12, 8.0).astype(np.int32) >> shift).astype(np.int16)
     _vs_oracle(x)
 
@@ -142,11 +125,10 @@ def test_streaming_split_equals_one_call():
     rx1 = sc.Receiver(192)
     whole = rx1.demod(x, trace=True, soft=True)
     rx2 = sc.Receiver(192)
-    parts = [rx2.demod(np.ascontiguousarray(x[:, a:b]), trace=True, soft=True)
-             for a, b in ((0, 5), (5, 6), (6, 7), (7, 16))]
+    parts = rxcheck.demod_in_calls(rx2, x, (5, 1, 1, 9))
     assert rx2.frames == 16
-    for k in ("bits", "valid", "trace", "soft"):
-        np.testing.assert_array_equal(np.concatenate([p[k] for p in parts], axis=1), whole[k])
+    for k in rxcheck.KEYS:
+        np.testing.assert_array_equal(parts[k], whole[k])
     rx2.reset()
     again = rx2.demod(x, trace=True, soft=True)
     np.testing.assert_array_equal(again["bits"], whole["bits"])
@@ -176,8 +158,8 @@ def test_device_api_torch():
     ds = torch.zeros((256, 10, 31, 2), dtype=torch.float32, device="cuda")
     rx.demod_device(dx, db, dv, dt, ds)
     torch.cuda.synchronize()
-    _assert_same({"bits": db.cpu().numpy(), "valid": dv.cpu().numpy(),
-                  "trace": dt.cpu().numpy(), "soft": ds.cpu().numpy()}, bits, valid, tr)
+    rxcheck.assert_same({"bits": db.cpu().numpy(), "valid": dv.cpu().numpy(),
+                         "trace": dt.cpu().numpy(), "soft": ds.cpu().numpy()}, (bits, valid, tr))
 
 
 @pytest.mark.parametrize("ebn0", [0.0, 3.0, 6.0, 10.0])
@@ -196,7 +178,7 @@ def test_full_size_c3():
     rx = sc.Receiver(nch)
     out = rx.demod(x, trace=True, soft=True)
     bits, valid, tr = oracle.cpu_rx(x, trace=True)
-    _assert_same(out, bits, valid, tr)
+    rxcheck.assert_same(out, (bits, valid, tr))
 
 
 @pytest.mark.parametrize("ebn0", [0.0, 5.0, 10.0])
@@ -209,7 +191,7 @@ def test_c5_awgn_full_channel_count(ebn0):
     rx = sc.Receiver(nch)
     out = rx.demod(x, trace=True)
     bits, valid, tr = oracle.cpu_rx(x, trace=True)
-    _assert_same(out, bits, valid, tr)
+    rxcheck.assert_same(out, (bits, valid, tr))
     assert 0 < valid.sum() < valid.size
 
 
@@ -246,7 +228,7 @@ def test_every_workgroup_shape(shape, monkeypatch):
     """rx_kernel<G, FP> (groups per workgroup x front waves per group) is chosen
     by batch size (pick_shape); QPSK_SHAPE forces each one on the same ragged
     batch."""
-    monkeypatch.setenv("QPSK_SHAPE", shape)
+    rxcheck.force_shape(monkeypatch, shape, None)
     x = oracle.synth(61, 300, 12, 5.0)
     _vs_oracle(x)
 
@@ -257,7 +239,7 @@ def test_split_fir_window_boundary(monkeypatch):
     part (dec[mi .. mi+162]) reaches them.  On a forced 4x2 batch every output
     must be exact, and the batch must hold valid frames on both sides of the
     boundary, the data symbols of the mi >= 93 ones read from the late pass."""
-    monkeypatch.setenv("QPSK_SHAPE", "4x2")
+    rxcheck.force_shape(monkeypatch, "4x2", None)
     x = oracle.synth(71, 512, 8, 8.0)
     out = _vs_oracle(x)
     mi = out["trace"][..., 0][out["valid"].astype(bool)]
@@ -276,13 +258,12 @@ def test_dual_chain_group_widths(width, monkeypatch):
     back layout: a quad of lanes per channel at W = 16 / 32 (back_frame_quad,
     W / 16 back waves per frame chain), a lane per channel at W = 64 (which
     also moves 2 channels between the front waves, pick_shape's split)."""
-    monkeypatch.setenv("QPSK_WIDTH", width)
+    rxcheck.force_shape(monkeypatch, None, width)
     x = oracle.synth(64, 333, 15, 4.0)
     _vs_oracle(x)
 
 
-@pytest.mark.parametrize("shape,width", [("4x2", None), ("2x4d", None), ("1x8", "64"),
-                                         ("1x8", "32"), ("1x8", "16")])
+@pytest.mark.parametrize("shape,width", rxcheck.ALL_SHAPES)
 def test_head_prepass(shape, width, monkeypatch):
     """SURVEY.md 8f rank 4, the frame-parallel FIR-head pre-pass
     (QPSK_HEADPASS=1): head_kernel computes every channel-frame's
@@ -290,9 +271,7 @@ def test_head_prepass(shape, width, monkeypatch):
     fronts copy it instead of filtering.  Every shape, a ragged AWGN batch
     with silent and saturated channels, every output exact."""
     monkeypatch.setenv("QPSK_HEADPASS", "1")
-    monkeypatch.setenv("QPSK_SHAPE", shape)
-    if width:
-        monkeypatch.setenv("QPSK_WIDTH", width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     x = oracle.synth(95, 300, 11, 5.0)
     x[7] = 0
     x[8] = 32767
@@ -307,12 +286,8 @@ def test_head_prepass_across_call_splits(monkeypatch):
     x = oracle.synth(96, nch, nf, 4.0)
     bits, valid, tr = oracle.cpu_rx(x, trace=True)
     rx = sc.Receiver(nch)
-    parts, a = [], 0
-    for b in (1, 2, 6, 7, nf):
-        parts.append(rx.demod(np.ascontiguousarray(x[:, a:b]), trace=True, soft=True))
-        a = b
-    out = {k: np.concatenate([p[k] for p in parts], axis=1) for k in ("bits", "valid", "trace", "soft")}
-    _assert_same(out, bits, valid, tr)
+    out = rxcheck.demod_in_calls(rx, x, (1, 1, 4, 1, nf - 7))
+    rxcheck.assert_same(out, (bits, valid, tr))
 
 
 @pytest.mark.parametrize("nch", [8192, 16384])
@@ -329,8 +304,7 @@ def test_quad_back_edges_and_noise(ebn0, width, monkeypatch):
     """The quad-per-channel back (160 channels: W = 16, or W = 32 forced) on
     saturated, zero and constant channels next to noisy ones (sign-of-zero and
     padding paths of back_frame_quad), every output exact."""
-    if width:
-        monkeypatch.setenv("QPSK_WIDTH", width)
+    rxcheck.force_shape(monkeypatch, None, width)
     x = oracle.synth(71, 160, 9, ebn0)
     x[3] = 0
     x[17] = 32767
@@ -346,8 +320,7 @@ def test_quad_back_exact_division(width, monkeypatch):
     forced: two back waves per frame chain): the exact retrain path, which a
     quad wave runs a lane per channel (back_frame_quad)."""
     monkeypatch.setenv("QPSK_FORCE_EXACT", "1")
-    if width:
-        monkeypatch.setenv("QPSK_WIDTH", width)
+    rxcheck.force_shape(monkeypatch, None, width)
     x = oracle.synth(72, 100, 8, 4.0)
     _vs_oracle(x)
 
@@ -439,13 +412,9 @@ def test_long_stream_crosses_the_keystream_period():
     x = oracle.synth(123, nch, nf, 1000.0)
     bits, valid, _ = oracle.cpu_rx(x)
     rx = sc.Receiver(nch)
-    outs, a = [], 0
-    for b in (300, 1, 499, 300):
-        outs.append(rx.demod(np.ascontiguousarray(x[:, a:a + b])))
-        a += b
+    out = rxcheck.demod_in_calls(rx, x, (300, 1, 499, 300), trace=False, soft=False)
     assert rx.frames == nf
-    np.testing.assert_array_equal(np.concatenate([o["valid"] for o in outs], 1), valid)
-    np.testing.assert_array_equal(np.concatenate([o["bits"] for o in outs], 1), bits)
+    rxcheck.assert_same(out, {"bits": bits, "valid": valid})
     assert valid[:, 1057:].any()
 
 
@@ -477,12 +446,8 @@ def test_random_batches_and_splits(seed):
     bits, valid, tr = oracle.cpu_rx(x, trace=True)
     cuts = sorted(set(int(c) for c in rng.integers(1, nf, size=2)))
     rx = sc.Receiver(nch)
-    parts, a = [], 0
-    for b in cuts + [nf]:
-        parts.append(rx.demod(np.ascontiguousarray(x[:, a:b]), trace=True, soft=True))
-        a = b
-    out = {k: np.concatenate([p[k] for p in parts], axis=1) for k in ("bits", "valid", "trace", "soft")}
-    _assert_same(out, bits, valid, tr)
+    out = rxcheck.demod_in_calls(rx, x, np.diff([0] + cuts + [nf]))
+    rxcheck.assert_same(out, (bits, valid, tr))
 
 
 @pytest.mark.parametrize("nch", [100, 333, 8192])
@@ -495,12 +460,8 @@ def test_quad_backs_across_call_splits(nch):
     x = oracle.synth(140 + nch, nch, nf, 5.0 if nch != 333 else 1000.0)
     bits, valid, tr = oracle.cpu_rx(x, trace=True)
     rx = sc.Receiver(nch)
-    parts, a = [], 0
-    for b in (1, 2, 6, 7, nf):
-        parts.append(rx.demod(np.ascontiguousarray(x[:, a:b]), trace=True, soft=True))
-        a = b
-    out = {k: np.concatenate([p[k] for p in parts], axis=1) for k in ("bits", "valid", "trace", "soft")}
-    _assert_same(out, bits, valid, tr)
+    out = rxcheck.demod_in_calls(rx, x, (1, 1, 4, 1, nf - 7))
+    rxcheck.assert_same(out, (bits, valid, tr))
 
 
 def _gpus():
@@ -520,7 +481,7 @@ def test_state_snapshot_resumes_exactly(mode):
     x = oracle.synth(150, nch, nf, 5.0)
     whole = sc.Receiver(nch, mode=mode).demod(x, trace=True, soft=True)
     bits, valid, tr = oracle.cpu_rx(x, trace=True, mode=mode)
-    _assert_same(whole, bits, valid, tr)
+    rxcheck.assert_same(whole, (bits, valid, tr))
     a = sc.Receiver(nch, mode=mode)
     first = a.demod(np.ascontiguousarray(x[:, :cut]), trace=True, soft=True)
     snap = a.state_save()

@@ -1,7 +1,6 @@
 """Records behind the receive (include/qpsk_compact.h): the context-bound calls,
 the record stream and the C example against the host compaction of the dense
 outputs that the plain calls give on the same input.  Run with -m gpu."""
-import ctypes as C
 import gc
 import os
 import subprocess
@@ -10,6 +9,8 @@ import numpy as np
 import pytest
 
 import singlecarrier_amd as sc
+from g711 import compress
+from rxcheck import live_handles
 
 pytestmark = pytest.mark.gpu
 
@@ -18,12 +19,6 @@ ORDERS = [sc.REC_BY_CHANNEL, sc.REC_BY_FRAME]
 # 300 channels take the quad backs, 4,500 the lane backs
 SHAPES = [(300, 12), (4500, 6)]
 EBN0 = 5.0
-
-
-def _live():
-    f = sc.lib().qpsk_hip_live_handles
-    f.restype, f.argtypes = C.c_long, []
-    return int(f())
 
 
 @pytest.fixture(scope="module")
@@ -111,7 +106,6 @@ def test_split_calls_concatenate(cases, order):
 
 @pytest.mark.parametrize("order", ORDERS)
 def test_format_call_on_interleaved_alaw(order):
-    from test_output_host import compress
     nch, nf = 130, 6
     x = sc.synth_device(43, nch, nf, EBN0).cpu().numpy()
     fmt = sc.IN_ALAW | sc.IN_INTERLEAVED
@@ -182,7 +176,7 @@ def test_record_stream_equals_plain_stream(order):
     nch, fpc, nchunk = 130, 4, 5
     x = sc.synth_device(44, nch, fpc * nchunk, EBN0).cpu().numpy()
     gc.collect()
-    live = _live()
+    live = live_handles()
     plain = sc.Stream(nch, fpc, nslot=3)
     dense = _feed(plain, x, fpc, nchunk, plain.retrieve)
     with pytest.raises(sc.QpskError) as ei:   # a record retrieve on a plain stream
@@ -202,7 +196,7 @@ def test_record_stream_equals_plain_stream(order):
     assert st.pending == 1
     st.retrieve_records()
     st.close()
-    assert _live() == live
+    assert live_handles() == live
     assert len(recs) == len(dense) == nchunk
     total = 0
     for (b, v), r in zip(dense, recs):

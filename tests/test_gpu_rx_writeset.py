@@ -21,15 +21,15 @@ launched or counted; those cases check the refusal, never a misaligned launch.
 The expectations come from three oracle runs of one input (one per receiver
 mode used) and a few small ones, shared by all cases and read-only.
 """
-import ctypes
 import functools
 
 import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
-from test_rx_plan import plan_limits, run_plan_check
+from plan_check import plan_limits, run_plan_check
 
 pytestmark = pytest.mark.gpu
 
@@ -38,18 +38,12 @@ FILLS = (0xA5, 0x5A)
 NAMES = ("in", "bits", "valid", "trace", "soft")
 # minimum legal start of each array past a 16-byte line
 START = {"in": 0, "bits": 2, "valid": 1, "trace": 0, "soft": 8}
-# the five forced (QPSK_SHAPE, QPSK_WIDTH) pairs of tests/test_gpu_frame_index.py and pick_shape's own choice
-SHAPES = [("4x2", None), ("2x4d", None), ("1x8", "64"), ("1x8", "32"), ("1x8", "16"), (None, None)]
+# every forced (QPSK_SHAPE, QPSK_WIDTH) pair and pick_shape's own choice
+SHAPES = rxcheck.ALL_SHAPES + [(None, None)]
 SHAPE_IDS = ["4x2", "2x4d", "1x8w64", "1x8w32", "1x8w16", "picked"]
 
 
 # ---------------------------------------------------------------- inputs and expectations
-def _frozen(d):
-    for a in d.values():
-        a.setflags(write=False)
-    return d
-
-
 @functools.lru_cache(maxsize=None)
 def _input(name):
     """int16 [nch][F][1880], read-only.  "noisy": 279 channels x 23 frames at
@@ -81,12 +75,9 @@ def _input(name):
 def _oracle(name, mode=sc.MODE_REFERENCE):
     """The oracle's outputs for _input(name) as the arrays a call writes."""
     x = _input(name)
-    bits, valid, tr = oracle.cpu_rx(x, trace=True, mode=mode)
-    trace = np.stack([tr["max_index"], tr["matches"], tr["valid"], tr["rx_timing"]], axis=-1).astype(np.int32)
-    soft = np.ascontiguousarray(tr["soft"], np.float32).copy()
-    soft[valid == 0] = 0.0
-    assert not bits[valid == 0].any()
-    return _frozen({"in": x, "bits": bits, "valid": valid, "trace": np.ascontiguousarray(trace), "soft": soft})
+    o = rxcheck.expected(x, mode)
+    assert not o["bits"][o["valid"] == 0].any()
+    return {"in": x, **o}
 
 
 def _expect(name, nch, F, mode=sc.MODE_REFERENCE, f0=0):
@@ -233,13 +224,6 @@ def _run(nch, F, name="noisy", mode=sc.MODE_REFERENCE, trace=True, soft=True, wh
     return exp
 
 
-def _force(monkeypatch, shape, width):
-    if shape:
-        monkeypatch.setenv("QPSK_SHAPE", shape)
-    if width:
-        monkeypatch.setenv("QPSK_WIDTH", width)
-
-
 # ---------------------------------------------------------------- the cases
 @pytest.mark.parametrize("F", [1, 2, 5])
 @pytest.mark.parametrize("nch", [1, 63, 65, 130, 257])
@@ -249,7 +233,7 @@ def test_every_back_on_ragged_channel_counts(shape, width, nch, F, monkeypatch):
     what pick_shape takes for these sizes): the lanes and quads past nch store
     nothing; F = 1, 2, 5 ends on either chain of the dual-chain shapes and on
     an odd tail."""
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     _run(nch, F, what=f"{shape}/{width}")
 
 
@@ -259,7 +243,7 @@ def test_every_back_on_ragged_channel_counts(shape, width, nch, F, monkeypatch):
 def test_optional_outputs(shape, width, soft, trace, monkeypatch):
     """An output that is not asked for is not written: its place in the buffer
     stays sentinel.  soft without trace runs nowhere else."""
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     _run(130, 5, trace=trace, soft=soft, what=f"{shape}/{width} trace={trace} soft={soft}")
 
 
@@ -277,7 +261,7 @@ def test_headpass(monkeypatch):
 def test_force_exact(shape, width, monkeypatch):
     """Every frame and every data job through the exact-division redo paths
     (train<true>, quad_redo_frame's job store, data_steps<true>)."""
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     monkeypatch.setenv("QPSK_FORCE_EXACT", "1")
     _run(130, 5, what=f"force exact {shape}")
 
@@ -287,7 +271,7 @@ def test_stale_outputs_are_overwritten(shape, width, monkeypatch):
     """A second call, on a fresh context and another input, into the same
     outputs as they were left: rows that were valid and are invalid now come
     out zero, everything equals the oracle's for the second input."""
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     nch, F = 130, 5
     first, second = _expect("noisy", nch, F), _expect("other", nch, F)
     for fill in FILLS:
@@ -310,7 +294,7 @@ def test_all_valid_mostly_valid_and_all_invalid(shape, width, name, f0, F, monke
     is rx_data_kernel's.  Noiseless input: most are.  White noise from its
     fourth frame on: no frame is valid, every row is the back waves' zeros and
     the data kernel has no job."""
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     _run(130, F, name=name, what=name, f0=f0)
 
 
@@ -340,13 +324,6 @@ def test_misaligned_pointers_are_refused(k, shift):
     finally:
         rx.close()
     g.check(exp, f"after refused {k}+{shift}")
-
-
-def _live():
-    """The library's count of live HIP allocations and handles (internal)."""
-    f = sc.lib().qpsk_hip_live_handles
-    f.restype = ctypes.c_long
-    return int(f())
 
 
 def test_misaligned_outputs_are_refused_through_the_format_call():
@@ -388,29 +365,25 @@ def test_the_format_call_refuses_in_front_of_its_conversion():
     fmt = sc.IN_ULAW | sc.IN_PLANAR
     codes = np.random.default_rng(4247).integers(0, 256, (nch, F * 1880), dtype=np.uint8)
     x = sc.input_convert_host(codes, fmt, nch)
-    bits, valid, tr = oracle.cpu_rx(x, trace=True)
-    soft = np.ascontiguousarray(tr["soft"], np.float32).copy()
-    soft[valid == 0] = 0.0
-    exp = {"bits": bits, "valid": valid, "soft": soft,
-           "trace": np.stack([tr["max_index"], tr["matches"], tr["valid"], tr["rx_timing"]], axis=-1)}
+    exp = rxcheck.expected(x)
     src = torch.from_numpy(codes).cuda()
     g = Guarded(nch, F, FILLS[1])
     rx = sc.Receiver(nch)
     try:
-        live = _live()
+        live = rxcheck.live_handles()
         for k, shift in (("trace", 8), ("soft", 4), ("bits", 1)):
             with pytest.raises(sc.QpskError) as e:
                 rx.demod_device_fmt(src, fmt, g.view("bits", shift if k == "bits" else 0), g.view("valid"),
                                     g.view("trace", shift if k == "trace" else 0),
                                     g.view("soft", shift if k == "soft" else 0))
             assert e.value.code == sc.QPSK_EINVAL
-            assert _live() == live
+            assert rxcheck.live_handles() == live
         torch.cuda.synchronize()
         assert rx.frames == 0
         g.check({}, "refused ulaw")
         rx.demod_device_fmt(src, fmt, g.view("bits"), g.view("valid"), g.view("trace"), g.view("soft"))
         rx.sync()
-        assert _live() > live and rx.frames == F
+        assert rxcheck.live_handles() > live and rx.frames == F
         g.check(exp, "after refused ulaw")
     finally:
         rx.close()
@@ -425,14 +398,14 @@ def test_the_record_call_refuses_in_front_of_its_buffers():
     g = Guarded(nch, F, FILLS[0], x=exp["in"])
     rx = sc.Receiver(nch)
     try:
-        live = _live()
+        live = rxcheck.live_handles()
         with pytest.raises(sc.QpskError) as e:
             rx.demod_records_device(g.view("in", 2), trace=True, soft=True)
         assert e.value.code == sc.QPSK_EINVAL
-        assert _live() == live and rx.frames == 0
+        assert rxcheck.live_handles() == live and rx.frames == 0
         o = rx.demod_records_device(g.view("in"), trace=True, soft=True)
         rx.sync()
-        assert _live() > live and rx.frames == F
+        assert rxcheck.live_handles() > live and rx.frames == F
         assert int(o["count"].cpu().numpy().view(np.uint32)[0]) == int(exp["valid"].sum())
     finally:
         rx.close()
@@ -443,7 +416,7 @@ def test_the_record_call_refuses_in_front_of_its_buffers():
 @pytest.fixture(scope="module")
 def limits(tmp_path_factory):
     """(kZeroCopyCF, the largest pinned cf) of csrc/qpsk_rx_plan.h, from a plain
-    build (no sanitizer) of the program of tests/test_rx_plan.py."""
+    build (no sanitizer) of the program of tests/plan_check.py."""
     return plan_limits(run_plan_check(tmp_path_factory.mktemp("plan"), sanitize=False))
 
 

@@ -14,40 +14,48 @@ whether the split FIR computes dec[255..289] and what the quad backs branch
 on; the second kind of pair lives on the launch boundary and the carried
 window, which the split calls and the checkpoint put between its two frames.
 
-Every comparison is exact, tests/test_gpu_carry.py's: bits, valid flags,
-max_index, matches, rx_timing, the soft symbols of valid frames, zeros
-elsewhere.  Expected values are the oracle's (oracle/cpu_ref.c), computed once
-per mode, and the oracle is pinned to the reference on this corpus.
+Every comparison with the oracle is tests/rxcheck.py's.  Expected values are
+the oracle's (oracle/cpu_ref.c), computed once per mode, and the oracle is
+pinned to the reference on this corpus.
 """
+import functools
+
 import numpy as np
 import pytest
 
+import rxcheck
 import singlecarrier_amd as sc
 import spacing
-from test_gpu_carry import KEYS, _assert_same, _force, _split
-from test_gpu_timing import CALLS, DIRECT, MODES, SHAPES
+from rxcheck import KEYS
+from timing import CALLS, DIRECT, MODES
 
 pytestmark = pytest.mark.gpu
 
-shapes = pytest.mark.parametrize("shape,width", SHAPES)
-some_shapes = pytest.mark.parametrize("shape,width", [(None, None), ("4x2", None)])
+shapes = pytest.mark.parametrize("shape,width", rxcheck.ALL_SHAPES)
+some_shapes = pytest.mark.parametrize("shape,width", [(None, None)] + rxcheck.ALL_SHAPES[:1])
 CUT = 5                          # frames before the checkpoint
 RANGE = slice(2304, 2816)        # the checkpoint's channels: directed and random ones
+
+
+@functools.lru_cache(maxsize=None)
+def _expected(mode):
+    """spacing.expected as dense outputs, converted once per mode, read-only"""
+    return rxcheck.frozen(rxcheck.dense(*spacing.expected(mode)))[0]
 
 
 def _run(mode, calls=None):
     x = spacing.corpus()
     rx = sc.Receiver(x.shape[0], mode=mode)
-    out = _split(rx, x, list(calls or [x.shape[1]]))
+    out = rxcheck.demod_in_calls(rx, x, calls or [x.shape[1]])
     assert rx.frames == x.shape[1]
     rx.close()
-    _assert_same(out, *spacing.expected(mode))
+    rxcheck.assert_same(out, _expected(mode), f"mode {mode}")
 
 
 @shapes
 @pytest.mark.parametrize("mode", MODES)
 def test_corpus_every_shape_and_mode(mode, shape, width, monkeypatch):
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     _run(mode)
 
 
@@ -55,7 +63,7 @@ def test_corpus_every_shape_and_mode(mode, shape, width, monkeypatch):
 def test_corpus_head_prepass(shape, width, monkeypatch):
     """head_kernel's FIR heads (QPSK_HEADPASS=1, reference mode) at every pair."""
     monkeypatch.setenv("QPSK_HEADPASS", "1")
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     _run(sc.MODE_REFERENCE)
 
 
@@ -66,7 +74,7 @@ def test_corpus_across_calls(calls, mode, shape, width, monkeypatch):
     """One frame per call throughout, and calls of 1, 1, 2, 1 and the rest:
     the frames of every pair B fall on both sides of a launch boundary, with
     the window and its preamble position carried in the context between."""
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     nf = spacing.NFRAMES
     _run(mode, [1] * nf if calls == "ones" else list(CALLS) + [nf - sum(CALLS)])
 
@@ -95,7 +103,7 @@ def test_checkpoint_in_the_middle(mode, monkeypatch):
     head = a.demod(np.ascontiguousarray(x[:, :CUT]), trace=True, soft=True)
     snap = a.state_save(RANGE.start, n)
     a.close()
-    monkeypatch.setenv("QPSK_SHAPE", "4x2")
+    rxcheck.force_shape(monkeypatch, "4x2", None)
     f = sc.Receiver(n, mode=mode)
     f.state_load(snap)
     assert f.frames == CUT
@@ -104,14 +112,13 @@ def test_checkpoint_in_the_middle(mode, monkeypatch):
     got = {k: np.concatenate([head[k][RANGE], rest[k]], axis=1) for k in KEYS}
     for k in KEYS:
         np.testing.assert_array_equal(got[k], whole[k][RANGE], err_msg=k)
-    _assert_same(got, *exp)
+    rxcheck.assert_same(got, {k: v[RANGE] for k, v in _expected(mode).items()}, f"mode {mode}")
 
 
 def test_corpus_through_the_stream():
     """sc.Stream, 3 slots, chunks of 2 frames, reference mode: bits and valid
     flags of the six chunks equal the oracle's."""
     x = spacing.corpus()
-    bits, valid, _ = spacing.expected(sc.MODE_REFERENCE)
     fpc, nslot = 2, 3
     st = sc.Stream(x.shape[0], fpc, nslot=nslot)
     got_b, got_v = [], []
@@ -127,8 +134,8 @@ def test_corpus_through_the_stream():
         got_b.append(b)
         got_v.append(v)
     st.close()
-    np.testing.assert_array_equal(np.concatenate(got_v, axis=1), valid)
-    np.testing.assert_array_equal(np.concatenate(got_b, axis=1), bits)
+    rxcheck.assert_same({"bits": np.concatenate(got_b, axis=1), "valid": np.concatenate(got_v, axis=1)},
+                        _expected(sc.MODE_REFERENCE))
 
 
 def test_corpus_forced_exact(monkeypatch):

@@ -23,16 +23,13 @@ import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
+from rxcheck import KEYS
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KEYS = ("bits", "valid", "trace", "soft")
-
-
-def _cat(parts):
-    return {k: np.concatenate([p[k] for p in parts], axis=1) for k in KEYS}
 
 
 def _raises(code, fn, *a):
@@ -84,8 +81,7 @@ def test_snapshot_is_a_function_of_the_channel_state(shape, monkeypatch):
     buffers hold other channels' entries past what the window uses; 4x2: the
     split FIR leaves dec[255..289] for mi < 93): the snapshots are equal byte
     for byte, and equal again when taken twice."""
-    if shape:
-        monkeypatch.setenv("QPSK_SHAPE", shape)
+    rxcheck.force_shape(monkeypatch, shape, None)
     nf = 9
     x = oracle.synth(161, 300, nf, 8.0)
     a, b = sc.Receiver(300), sc.Receiver(100)
@@ -160,9 +156,7 @@ def test_snapshot_crosses_processes(tmp_path):
         assert r.returncode == 0, r.stderr[-3000:]
     whole = sc.Receiver(nch).demod(x, trace=True, soft=True)
     parts = [dict(np.load(tmp_path / f"{s}.npz")) for s in ("save", "load")]
-    got = _cat(parts)
+    got = {k: np.concatenate([p[k] for p in parts], axis=1) for k in KEYS}
     for k in KEYS:
         np.testing.assert_array_equal(got[k], whole[k])
-    bits, valid, tr = oracle.cpu_rx(x, trace=True)
-    np.testing.assert_array_equal(got["bits"], bits)
-    np.testing.assert_array_equal(got["valid"], valid)
+    rxcheck.assert_same(got, oracle.cpu_rx(x, trace=True))

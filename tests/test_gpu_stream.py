@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
 
 pytestmark = pytest.mark.gpu
@@ -30,8 +31,8 @@ def test_stream_equals_one_batch(nslot):
         got_b.append(b)
         got_v.append(v)
     st.close()
-    assert (np.concatenate(got_v, axis=1) == ev).all()
-    assert (np.concatenate(got_b, axis=1) == eb).all()
+    rxcheck.assert_same({"bits": np.concatenate(got_b, axis=1), "valid": np.concatenate(got_v, axis=1)},
+                        {"bits": eb, "valid": ev})
     assert ev.any()
 
 
@@ -214,5 +215,5 @@ def test_stream_in_variant_modes(mode):
         got_b.append(b)
         got_v.append(v)
     st.close()
-    assert (np.concatenate(got_v, axis=1) == ev).all()
-    assert (np.concatenate(got_b, axis=1) == eb).all()
+    rxcheck.assert_same({"bits": np.concatenate(got_b, axis=1), "valid": np.concatenate(got_v, axis=1)},
+                        {"bits": eb, "valid": ev})

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
 
 pytestmark = pytest.mark.gpu
@@ -60,7 +61,7 @@ def test_rx_on_device_synthesised_input():
     rx.demod_device(x, bits, valid)
     torch.cuda.synchronize()
     eb, ev, _ = oracle.cpu_rx(x.cpu().numpy())
-    assert (valid.cpu().numpy() == ev).all() and (bits.cpu().numpy() == eb).all()
+    rxcheck.assert_same({"bits": bits.cpu().numpy(), "valid": valid.cpu().numpy()}, {"bits": eb, "valid": ev})
     assert ev.any()
     rx.close()
 

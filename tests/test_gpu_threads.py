@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
 
 pytestmark = pytest.mark.gpu
@@ -56,12 +57,9 @@ def test_contexts_from_four_host_threads():
             start.wait()
             rx = sc.Receiver(x.shape[0], device=t % ndev, mode=JOBS[t][4])
             nf = x.shape[1]
-            parts = []
-            for a, b in ((0, 2), (2, 3), (3, nf)):
-                parts.append(rx.demod(np.ascontiguousarray(x[:, a:b]), trace=True, soft=True))
+            outs[t] = rxcheck.demod_in_calls(rx, x, (2, 1, nf - 3))
             assert rx.frames == nf
             rx.close()
-            outs[t] = {k: np.concatenate([p[k] for p in parts], axis=1) for k in parts[0]}
         except BaseException as e:   # re-raised in the main thread
             errs[t] = e
 
@@ -76,13 +74,7 @@ def test_contexts_from_four_host_threads():
         assert outs[t] is not None, f"thread {t} did not finish"
     for t, x in enumerate(xs):
         bits, valid, tr = oracle.cpu_rx(x, trace=True, mode=JOBS[t][4])
-        o = outs[t]
-        np.testing.assert_array_equal(o["valid"], valid, err_msg=f"thread {t}")
-        np.testing.assert_array_equal(o["bits"], bits, err_msg=f"thread {t}")
-        np.testing.assert_array_equal(o["trace"][..., 0], tr["max_index"])
-        np.testing.assert_array_equal(o["trace"][..., 3], tr["rx_timing"])
-        vm = valid.astype(bool)
-        np.testing.assert_array_equal(o["soft"][vm], tr["soft"][vm])
+        rxcheck.assert_same(outs[t], (bits, valid, tr), f"thread {t}")
         assert 0 < valid.sum() < valid.size
 
 
@@ -154,8 +146,7 @@ def test_streams_from_three_host_threads():
         if errs[t] is not None:
             raise errs[t]
         bits, valid, _ = oracle.cpu_rx(xs[t])
-        np.testing.assert_array_equal(outs[t][1], valid, err_msg=f"thread {t}")
-        np.testing.assert_array_equal(outs[t][0], bits, err_msg=f"thread {t}")
+        rxcheck.assert_same({"bits": outs[t][0], "valid": outs[t][1]}, {"bits": bits, "valid": valid}, f"thread {t}")
         assert valid.any()
 
 

@@ -12,45 +12,47 @@ asserts, on the oracle alone, what they reach:
   all of them undecided by the filtered hunt, so that the exact chain's
   first-lag rule (and fft_hunt's) decides max_index, on valid frames.
 
-Every comparison is exact, tests/test_gpu_carry.py's: bits, valid flags,
-max_index, matches, rx_timing, the soft symbols of valid frames, zeros
-elsewhere.  Expected values are the oracle's (oracle/cpu_ref.c), computed once
-per corpus and mode.
+Every comparison is tests/rxcheck.py's.  Expected values are the oracle's
+(oracle/cpu_ref.c), computed once per corpus and mode.
 """
+import functools
+
 import numpy as np
 import pytest
 
+import rxcheck
 import singlecarrier_amd as sc
 import timing
-from test_gpu_carry import _assert_same, _force, _split
+from timing import CALLS, DIRECT, MODES
 
 pytestmark = pytest.mark.gpu
 
-# (QPSK_SHAPE, QPSK_WIDTH): the five of tests/test_gpu_frame_index.py
-SHAPES = [("4x2", None), ("2x4d", None), ("1x8", "64"), ("1x8", "32"), ("1x8", "16")]
-MODES = [sc.MODE_REFERENCE, sc.MODE_DEC752, sc.MODE_FFT_HUNT, sc.MODE_DEC752 | sc.MODE_FFT_HUNT]
-DIRECT = [sc.MODE_REFERENCE, sc.MODE_DEC752]
-assert MODES == [0, 1, 2, 3]   # the oracle's mode numbers are the library's
+assert MODES == [sc.MODE_REFERENCE, sc.MODE_DEC752, sc.MODE_FFT_HUNT, sc.MODE_DEC752 | sc.MODE_FFT_HUNT]
 
-shapes = pytest.mark.parametrize("shape,width", SHAPES)
-some_shapes = pytest.mark.parametrize("shape,width", [(None, None), ("4x2", None)])
-CALLS = (1, 1, 2, 1)           # then the remaining frames
+shapes = pytest.mark.parametrize("shape,width", rxcheck.ALL_SHAPES)
+some_shapes = pytest.mark.parametrize("shape,width", [(None, None)] + rxcheck.ALL_SHAPES[:1])
+
+
+@functools.lru_cache(maxsize=None)
+def _expected(name, mode):
+    """timing.expected as dense outputs, converted once per corpus and mode, read-only"""
+    return rxcheck.frozen(rxcheck.dense(*timing.expected(name, mode)))[0]
 
 
 def _run(name, mode, calls=None):
     x = timing.corpus(name)
     rx = sc.Receiver(x.shape[0], mode=mode)
-    out = _split(rx, x, list(calls or [x.shape[1]]))
+    out = rxcheck.demod_in_calls(rx, x, calls or [x.shape[1]])
     assert rx.frames == x.shape[1]
     rx.close()
-    _assert_same(out, *timing.expected(name, mode))
+    rxcheck.assert_same(out, _expected(name, mode), f"{name}, mode {mode}")
 
 
 @shapes
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("name", ["sweep", "sweep_noisy", "impulses"])
 def test_corpus_every_shape_and_mode(name, mode, shape, width, monkeypatch):
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     _run(name, mode)
 
 
@@ -59,7 +61,7 @@ def test_sweep_head_prepass(shape, width, monkeypatch):
     """head_kernel's FIR heads (QPSK_HEADPASS=1, reference mode) at every
     rx_timing and preamble position."""
     monkeypatch.setenv("QPSK_HEADPASS", "1")
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     _run("sweep", sc.MODE_REFERENCE)
 
 
@@ -69,7 +71,7 @@ def test_sweep_head_prepass(shape, width, monkeypatch):
 def test_corpus_across_calls(name, mode, shape, width, monkeypatch):
     """Calls of 1, 1, 2, 1 and the remaining frames: ties and every rx_timing
     cross call boundaries and the carried history."""
-    _force(monkeypatch, shape, width)
+    rxcheck.force_shape(monkeypatch, shape, width)
     nf = timing.corpus(name).shape[1]
     calls = [f for k, f in enumerate(CALLS) if sum(CALLS[:k + 1]) <= nf]
     if nf > sum(calls):
@@ -87,9 +89,9 @@ def test_impulses_tiny_host_calls(which, mode):
     ch = np.arange(16) if which == "first16" else timing.tied_channels(mode)
     x = np.ascontiguousarray(timing.impulses()[ch])
     rx = sc.Receiver(16, mode=mode)
-    out = _split(rx, x, [1] * x.shape[1])
+    out = rxcheck.demod_in_calls(rx, x, [1] * x.shape[1])
     rx.close()
-    _assert_same(out, *(a[ch] for a in timing.expected("impulses", mode)))
+    rxcheck.assert_same(out, {k: v[ch] for k, v in _expected("impulses", mode).items()}, which)
 
 
 def test_impulses_forced_exact(monkeypatch):

@@ -6,8 +6,9 @@ import numpy as np
 import pytest
 
 import oracle
+import rxcheck
 import singlecarrier_amd as sc
-from test_tx_batch import golden_payload, packet_calls, with_gaps
+from tx_geometry import golden_payload, packet_calls, with_gaps
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -142,8 +143,7 @@ def test_transmit_into_receive_on_the_device():
     torch.cuda.synchronize()
     rx.sync()
     np.testing.assert_array_equal(out.cpu().numpy(), x)
-    np.testing.assert_array_equal(d_valid.cpu().numpy(), ev)
-    np.testing.assert_array_equal(d_bits.cpu().numpy(), eb)
+    rxcheck.assert_same({"bits": d_bits.cpu().numpy(), "valid": d_valid.cpu().numpy()}, {"bits": eb, "valid": ev})
     tx.close()
     rx.close()
 

@@ -12,7 +12,7 @@ import pytest
 
 import singlecarrier_amd as sc
 import tx_geometry as g
-from test_output_host import CODES, compress
+from g711 import CODES, compress
 from tx_geometry import CASES
 
 pytestmark = pytest.mark.gpu

@@ -11,40 +11,12 @@ import numpy as np
 import pytest
 
 import singlecarrier_amd as sc
+from g711 import alaw_table, expand, ulaw_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "singlecarrier_amd", "csrc")
 SHAPES = [(1, 1), (3, 7), (63, 63), (65, 80), (130, 131)]
 ENCS = [sc.IN_S16, sc.IN_ALAW, sc.IN_ULAW]
-
-
-def ulaw_table():
-    """ITU-T G.711 mu-law, all 256 codes, written out here"""
-    t = np.zeros(256, np.int64)
-    for code in range(256):
-        u = ~code & 0xFF
-        m = (((u & 15) << 3) + 0x84) << ((u >> 4) & 7)
-        t[code] = 0x84 - m if u & 0x80 else m - 0x84
-    return t
-
-
-def alaw_table():
-    """ITU-T G.711 A-law, all 256 codes, written out here"""
-    t = np.zeros(256, np.int64)
-    for code in range(256):
-        a = code ^ 0x55
-        m, s = (a & 15) << 4, (a >> 4) & 7
-        v = m + 8 if s == 0 else m + 0x108 if s == 1 else (m + 0x108) << (s - 1)
-        t[code] = v if a & 0x80 else -v
-    return t
-
-
-TABLES = {sc.IN_ALAW: alaw_table(), sc.IN_ULAW: ulaw_table()}
-
-
-def expand(block, enc):
-    """source elements -> int16, by this file's tables"""
-    return block.astype(np.int16) if enc == sc.IN_S16 else TABLES[enc][block].astype(np.int16)
 
 
 def source(rng, enc, n, offset):

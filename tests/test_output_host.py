@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import singlecarrier_amd as sc
-from test_input_host import TABLES
+from g711 import ALL, CODES, TABLES, compress
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "singlecarrier_amd", "csrc")
@@ -18,42 +18,6 @@ ENCS = [sc.OUT_S16, sc.OUT_ALAW, sc.OUT_ULAW]
 NCHS = [1, 63, 64, 65, 130]
 NS = [1, 127, 128, 129, 2783]
 SENTINEL = 0xC3
-
-
-def _msb(v):
-    return v.bit_length() - 1
-
-
-def ulaw_compress(x):
-    """ITU-T G.191 ulaw_compress on a 16-bit sample, written out here"""
-    m = (~x >> 2) if x < 0 else (x >> 2)
-    a = min(m + 33, 0x1FFF)
-    s = _msb(a) - 4
-    assert 1 <= s <= 8
-    code = ((8 - s) << 4) | (15 - ((a >> s) & 15))
-    return code | 0x80 if x >= 0 else code
-
-
-def alaw_compress(x):
-    """ITU-T G.191 alaw_compress on a 16-bit sample, written out here"""
-    m = (~x >> 4) if x < 0 else (x >> 4)
-    v = m
-    if m >= 16:
-        e = _msb(m) - 3
-        v = (m >> (e - 1)) - 16 + (e << 4)
-    if x >= 0:
-        v |= 0x80
-    return v ^ 0x55
-
-
-ALL = np.arange(-32768, 32768, dtype=np.int64)
-CODES = {sc.OUT_ALAW: np.array([alaw_compress(int(x)) for x in ALL], np.uint8),
-         sc.OUT_ULAW: np.array([ulaw_compress(int(x)) for x in ALL], np.uint8)}
-
-
-def compress(x, enc):
-    """int16 samples -> elements of the encoding, by this file's formulas"""
-    return x.astype(np.int16) if enc == sc.OUT_S16 else CODES[enc][x.astype(np.int64) + 32768]
 
 
 def lib_codes(enc):

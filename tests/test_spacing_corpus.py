@@ -41,7 +41,6 @@ import pytest
 import oracle
 import spacing
 import timing
-from test_timing_corpus import _same_as_reference
 
 ALL_MODES = [0, 1, 2, 3]
 DIRECT = [oracle.MODE_REF, oracle.MODE_DEC752]
@@ -165,7 +164,7 @@ def test_oracle_equals_the_reference_on_the_corpus(mode):
     bit."""
     if not oracle.ref_available(mode):
         pytest.skip("reference build not present")
-    assert _same_as_reference(spacing.corpus(), mode, "spacing") > 0
+    assert timing.same_as_reference(spacing.corpus(), mode, "spacing") > 0
 
 
 @pytest.mark.parametrize("mode", DIRECT)

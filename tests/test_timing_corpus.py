@@ -90,19 +90,6 @@ def _impulse_ties(hc, mode):
     assert sp[timing.tied_channels(mode)].any(axis=1).all()
 
 
-def _same_as_reference(x, mode, what):
-    bits, valid, tr = oracle.cpu_rx(x, trace=True, mode=mode)
-    rbits, rvalid, rtr = oracle.ref_rx(x, trace=True, mode=mode)
-    np.testing.assert_array_equal(valid, rvalid, err_msg=what)
-    np.testing.assert_array_equal(bits, rbits, err_msg=what)
-    for k in ("max_index", "matches", "valid", "rx_timing"):
-        np.testing.assert_array_equal(tr[k], rtr[k], err_msg=f"{what}: {k}")
-    vm = valid.astype(bool)
-    np.testing.assert_array_equal(tr["soft"][vm].view(np.uint32), rtr["soft"][vm].view(np.uint32),
-                                  err_msg=what)
-    return int(vm.sum())
-
-
 @pytest.mark.parametrize("mode", DIRECT)
 def test_oracle_equals_the_reference_on_the_corpora(mode):
     """The unmodified reference against the restatement on the impulses (exact
@@ -110,6 +97,6 @@ def test_oracle_equals_the_reference_on_the_corpora(mode):
     flags, the trace and the soft symbols of valid frames, bit for bit."""
     if not oracle.ref_available(mode):
         pytest.skip("reference build not present")
-    assert _same_as_reference(timing.impulses(), mode, "impulses") > 0
+    assert timing.same_as_reference(timing.impulses(), mode, "impulses") > 0
     for name in ("sweep", "sweep_noisy"):
-        assert _same_as_reference(timing.corpus(name)[::16], mode, name) > 0
+        assert timing.same_as_reference(timing.corpus(name)[::16], mode, name) > 0

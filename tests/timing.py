@@ -35,6 +35,7 @@ import functools
 import numpy as np
 
 import oracle
+from rxcheck import frozen
 
 FRAME = 1880
 PERIOD = 640 + 8 * 31 * 5 + 903    # samples from one packet's start to the next
@@ -44,12 +45,12 @@ IMPULSE_STEP = 7
 RT_INITIAL = 3                     # FINE_TIMING_OFFSET, a fresh channel's rx_timing
 assert PERIOD == 2783
 
-
-def _frozen(*arrays):
-    for a in arrays:
-        if a is not None:
-            a.setflags(write=False)
-    return arrays
+# what tests/test_gpu_timing.py and tests/test_gpu_spacing.py run on: receiver modes (the oracle's
+# numbers are the library's), the two whose hunt hunt_classes restates, and the frames of a split
+# stream's first calls (then the remaining frames)
+MODES = [0, 1, 2, 3]
+DIRECT = [oracle.MODE_REF, oracle.MODE_DEC752]
+CALLS = (1, 1, 2, 1)
 
 
 @functools.lru_cache(maxsize=None)
@@ -58,7 +59,7 @@ def base(nf=6):
     s = oracle.synth(SEED, 1, nf + 3)[0].reshape(-1)
     nz = np.flatnonzero(s)
     assert nz.size and s.size - nz[0] >= nf * FRAME
-    return _frozen(s[nz[0]:].copy())[0]
+    return frozen(s[nz[0]:].copy())[0]
 
 
 @functools.lru_cache(maxsize=None)
@@ -68,7 +69,7 @@ def sweep(nf=6):
     x = np.zeros((PERIOD, n), np.int16)
     for d in range(PERIOD):
         x[d, d:] = b[:n - d]
-    return _frozen(x.reshape(PERIOD, nf, FRAME))[0]
+    return frozen(x.reshape(PERIOD, nf, FRAME))[0]
 
 
 @functools.lru_cache(maxsize=None)
@@ -77,7 +78,7 @@ def sweep_noisy(nf=6, ebn0=4.0):
     y -= oracle.synth(SEED + 1, PERIOD, nf, 1000.0)    # the noise alone, int32
     y += sweep(nf)
     np.clip(y, -32768, 32767, out=y)
-    return _frozen(y.astype(np.int16))[0]
+    return frozen(y.astype(np.int16))[0]
 
 
 @functools.lru_cache(maxsize=None)
@@ -89,7 +90,7 @@ def impulses(nf=4):
         for c, t in enumerate(ts):
             x[k, c, 1, t] = a
             x[k, c, 2, (3 * t) % FRAME] = -a
-    return _frozen(x.reshape(-1, nf, FRAME))[0]
+    return frozen(x.reshape(-1, nf, FRAME))[0]
 
 
 CORPORA = {"sweep": sweep, "sweep_noisy": sweep_noisy, "impulses": impulses}
@@ -102,7 +103,22 @@ def corpus(name):
 @functools.lru_cache(maxsize=None)
 def expected(name, mode=0):
     """The oracle's (bits, valid, trace) for a corpus, computed once, read-only."""
-    return _frozen(*oracle.cpu_rx(corpus(name), trace=True, mode=mode))
+    return frozen(*oracle.cpu_rx(corpus(name), trace=True, mode=mode))
+
+
+def same_as_reference(x, mode, what):
+    """The oracle against the unmodified reference on x, bit for bit; returns
+    the number of valid frames."""
+    bits, valid, tr = oracle.cpu_rx(x, trace=True, mode=mode)
+    rbits, rvalid, rtr = oracle.ref_rx(x, trace=True, mode=mode)
+    np.testing.assert_array_equal(valid, rvalid, err_msg=what)
+    np.testing.assert_array_equal(bits, rbits, err_msg=what)
+    for k in ("max_index", "matches", "valid", "rx_timing"):
+        np.testing.assert_array_equal(tr[k], rtr[k], err_msg=f"{what}: {k}")
+    vm = valid.astype(bool)
+    np.testing.assert_array_equal(tr["soft"][vm].view(np.uint32), rtr["soft"][vm].view(np.uint32),
+                                  err_msg=what)
+    return int(vm.sum())
 
 
 def rt_in(tr):
@@ -219,4 +235,4 @@ def tied_channels(mode=0, n=16):
     hc = hunt_classes(impulses(), mode)
     ch = np.flatnonzero((hc["split"] & ~hc["zero"]).any(axis=1))[:n]
     assert ch.size == n
-    return _frozen(ch)[0]
+    return frozen(ch)[0]

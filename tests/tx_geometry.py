@@ -28,11 +28,18 @@ packets_for_every_residue(gap)
                 one of each alignment, have fallen on every lo mod P (a row's
                 start, tile 0, is no cut).
 CASES           the sweeps of tests/test_gpu_tx_sweep.py by name.
+
+At the end, what tests/test_tx_batch.py and tests/test_gpu_tx.py share: the
+reference-made golden as a payload, and a payload as the reference's
+transmitter calls (golden_payload, packet_calls, with_gaps).
 """
 import functools
+import os
 from dataclasses import dataclass
 
 import numpy as np
+
+import oracle
 
 TX_PACKET = 1880      # transmitted samples of a packet; the gap follows them
 TILE = 2048           # elements of a row per block
@@ -243,3 +250,45 @@ CASES = {
 GRID_X_NCH = (8, 127, 128, 129, 257)   # a block row is 128 channels: 8 classes x 16 looped
 for _nch in GRID_X_NCH:
     CASES[f"gridx_{_nch}"] = Case(_nch, 2, 903, addr16=2)
+
+
+# ---------------------------------------------------------------- payloads and the reference's calls
+def golden_payload(golden_dir):
+    """tx_golden.npz (three packets back to back, 27 transmitter calls, no gap)
+    as a payload [1][3][8][62] and its samples: I-bit = re < 0, Q-bit = im < 0,
+    bits[2s] = Q, bits[2s+1] = I."""
+    g = np.load(os.path.join(golden_dir, "tx_golden.npz"))
+    assert list(g["lengths"]) == [128] + [31] * 8 + [128] + [31] * 8 + [128] + [31] * 8
+    syms = np.split(g["symbols"], np.cumsum(g["lengths"])[:-1])
+    bits = np.zeros((1, 3, 8, 62), np.uint8)
+    for n, (s, pre) in enumerate(zip(syms, g["preamble"])):
+        assert bool(pre) == (n % 9 == 0)
+        if not pre:
+            bits[0, n // 9, n % 9 - 1, 0::2] = s.imag < 0
+            bits[0, n // 9, n % 9 - 1, 1::2] = s.real < 0
+    return bits, g["samples"]
+
+
+def packet_calls(bits):
+    """One channel's payload [npackets][8][62] as the transmitter calls of the
+    reference's main(): [(symbols, is_preamble), ...], 9 per packet."""
+    pre = oracle.preamble().astype(np.float32)
+    calls = []
+    for pk in bits:
+        calls.append((pre + 1j * pre, True))
+        for fr in pk:
+            i = np.where(fr[1::2] == 1, -1.0, 1.0)
+            q = np.where(fr[0::2] == 1, -1.0, 1.0)
+            calls.append(((i + 1j * q).astype(np.complex64), False))
+    return calls
+
+
+def with_gaps(calls_out, gap):
+    """The samples of a list of per-call outputs with `gap` zeros after every
+    9th call (the reference fwrites them, src/qpsk.c:410-412)."""
+    parts = []
+    for n, o in enumerate(calls_out):
+        parts.append(o)
+        if n % 9 == 8:
+            parts.append(np.zeros(gap, np.int16))
+    return np.concatenate(parts)
