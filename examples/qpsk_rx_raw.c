@@ -4,7 +4,7 @@
  *
  *   qpsk_rx_raw in.raw out.bin            single channel, qpsk_rx_frame() per frame
  *                                          (unchanged reference call pattern)
- *   qpsk_rx_raw -b [-m MODE] [-f FMT] in1.raw [in2.raw ...] -o PREFIX
+ *   qpsk_rx_raw -b [-m MODE] [-f FMT] [-q DBFS] in1.raw [in2.raw ...] -o PREFIX
  *                                          every file is one channel; all channels are
  *                                          demodulated together through qpsk_rx_batch()
  *                                          and PREFIX<i>.bin is written per channel;
@@ -13,7 +13,13 @@
  *                                          FMT = s16 (default), alaw or ulaw: the files
  *                                          hold 8-bit G.711 codes, 1880 to a frame, which
  *                                          cross PCIe as they are and are expanded on the
- *                                          GPU (qpsk_rx_batch_fmt, qpsk_input.h)
+ *                                          GPU (qpsk_rx_batch_fmt, qpsk_input.h);
+ *                                          -q DBFS squelches at that input level (dB
+ *                                          relative to full scale, e.g. -60): frames of
+ *                                          idle channels, which the reference calls
+ *                                          valid, give no record (qpsk_level.h: the
+ *                                          meter, the squelch and the compaction run on
+ *                                          the GPU, qpsk_rx_batch_records_squelch)
  *   qpsk_rx_raw -f FMT in.g711 out.bin     one channel of G.711 codes, the same way
  * Output: one 496-byte record per valid frame, bits in bytes 0..61 (the
  * reference's /tmp/databits.txt format, src/qpsk.c:455-457).
@@ -24,8 +30,10 @@
 #include <string.h>
 
 #include "qpsk_batch.h"
+#include "qpsk_compact.h"
 #include "qpsk_input.h"
 #include "qpsk_internal.h"
+#include "qpsk_level.h"
 
 /* the whole frames of a file whose samples are `es` bytes each */
 static void *read_frames(const char *path, size_t es, int *nframes) {
@@ -68,8 +76,51 @@ static int single(const char *in, const char *out) {
     return 0;
 }
 
-/* prefix: PREFIX<i>.bin per channel; else one channel to the file `single_out` */
-static int batch(int nch, char **paths, const char *prefix, const char *single_out, int mode, int fmt) {
+/* The same output files behind the squelch: the receive, the level meter, the
+ * squelch at min_sumsq and the compaction on the GPU; the records that come
+ * back are the frames to write, by channel.  G.711 codes are expanded here
+ * first (the record call with squelch takes int16). */
+static int squelched(qpsk_ctx *ctx, int nch, int nf, const char *in, int fmt, uint64_t min_sumsq,
+                     const char *prefix) {
+    const size_t cf = (size_t)nch * nf;
+    int16_t *x = NULL;
+    if (fmt != QPSK_IN_S16) {
+        x = malloc(sizeof(int16_t) * cf * FRAME_SIZE);
+        const int err = qpsk_input_convert_host(fmt | QPSK_IN_PLANAR, in, 0, nch, nf, x, 1);
+        if (err) {
+            fprintf(stderr, "qpsk: %s\n", qpsk_strerror(err));
+            return 3;
+        }
+    }
+    qpsk_frame_rec *recs = malloc(sizeof *recs * cf);
+    uint32_t *groups = malloc(sizeof *groups * ((size_t)nch + 1)), count = 0;
+    const int err = qpsk_rx_batch_records_squelch(ctx, x ? x : (const int16_t *)in, nf, min_sumsq, NULL,
+                                                  QPSK_REC_BY_CHANNEL, cf, recs, NULL, NULL, groups, &count, NULL);
+    if (err) {
+        fprintf(stderr, "qpsk: %s\n", qpsk_strerror(err));
+        return 3;
+    }
+    uint8_t rec[BITS_PER_FRAME];
+    for (int c = 0; c < nch; c++) {
+        char name[4096];
+        snprintf(name, sizeof name, "%s%d.bin", prefix, c);
+        FILE *fo = fopen(name, "wb");
+        if (!fo) return 1;
+        for (uint32_t k = groups[c]; k < groups[c + 1]; k++) {
+            memset(rec, 0, sizeof rec);
+            qpsk_bits_unpack_host(&recs[k].bits, 1, rec);
+            fwrite(rec, 1, sizeof rec, fo);
+        }
+        fclose(fo);
+    }
+    free(x), free(recs), free(groups);
+    return 0;
+}
+
+/* prefix: PREFIX<i>.bin per channel; else one channel to the file `single_out`;
+ * squelch_db: NULL, or the level of -q */
+static int batch(int nch, char **paths, const char *prefix, const char *single_out, int mode, int fmt,
+                 const char *squelch_db) {
     int nf = -1;
     const size_t es = fmt == QPSK_IN_S16 ? sizeof(int16_t) : 1;
     void **ch = calloc((size_t)nch, sizeof(void *));
@@ -89,6 +140,11 @@ static int batch(int nch, char **paths, const char *prefix, const char *single_o
     if (!ctx) {
         fprintf(stderr, "qpsk: %s\n", qpsk_strerror(err));
         return 3;
+    }
+    if (squelch_db) {
+        err = squelched(ctx, nch, nf, in, fmt, qpsk_level_sumsq_of_dbfs(atof(squelch_db)), prefix);
+        qpsk_rx_destroy(ctx);
+        return err;
     }
     err = qpsk_rx_batch_fmt(ctx, in, fmt | QPSK_IN_PLANAR, 0, nf, bits, valid, NULL, NULL);
     if (err) {
@@ -121,7 +177,7 @@ static int format_of(const char *name) {
 
 int main(int argc, char **argv) {
     if (argc == 5 && !strcmp(argv[1], "-f") && format_of(argv[2]) >= 0)
-        return batch(1, argv + 3, NULL, argv[4], QPSK_MODE_REFERENCE, format_of(argv[2]));
+        return batch(1, argv + 3, NULL, argv[4], QPSK_MODE_REFERENCE, format_of(argv[2]), NULL);
     if (argc >= 3 && strcmp(argv[1], "-b") != 0 && strcmp(argv[1], "-f") != 0) return single(argv[1], argv[2]);
     if (argc >= 5 && !strcmp(argv[1], "-b") && !strcmp(argv[argc - 2], "-o")) {
         int first = 2, mode = QPSK_MODE_REFERENCE, fmt = QPSK_IN_S16;
@@ -133,9 +189,14 @@ int main(int argc, char **argv) {
             fmt = format_of(argv[first + 1]);
             first += 2;
         }
-        if (fmt >= 0) return batch(argc - 2 - first, argv + first, argv[argc - 1], NULL, mode, fmt);
+        const char *squelch_db = NULL;
+        if (argc >= first + 5 && !strcmp(argv[first], "-q")) {
+            squelch_db = argv[first + 1];
+            first += 2;
+        }
+        if (fmt >= 0) return batch(argc - 2 - first, argv + first, argv[argc - 1], NULL, mode, fmt, squelch_db);
     }
-    fprintf(stderr, "usage: %s in.raw out.bin | -f FMT in.g711 out.bin | -b [-m MODE] [-f FMT] in1.raw "
+    fprintf(stderr, "usage: %s in.raw out.bin | -f FMT in.g711 out.bin | -b [-m MODE] [-f FMT] [-q DBFS] in1.raw "
                     "[in2.raw ...] -o PREFIX   (FMT: s16, alaw, ulaw)\n", argv[0]);
     return 2;
 }

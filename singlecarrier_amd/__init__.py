@@ -4,8 +4,9 @@ Python mirror of the C-ABI in ``include/qpsk_internal.h`` (the reference's
 ``headers/qpsk_internal.h:79-84`` surface) and ``include/qpsk_batch.h`` (the
 batched, multi-channel receiver), ``include/qpsk_tx.h`` (the batched
 transmitter), ``include/qpsk_input.h`` (G.711 and timeslot-interleaved
-input), ``include/qpsk_output.h`` (the same formats as output) and
-``include/qpsk_compact.h`` (the receive output as records of the valid frames),
+input), ``include/qpsk_output.h`` (the same formats as output),
+``include/qpsk_compact.h`` (the receive output as records of the valid frames)
+and ``include/qpsk_level.h`` (the input level meter and the squelch),
 over ``singlecarrier_amd/libqpsk_hip.so``.
 
 There is no CPU fallback: if the HIP library is missing or no GPU is present,
@@ -209,6 +210,18 @@ def lib():
         L.qpsk_stream_create_records.restype = vp
         L.qpsk_stream_create_records.argtypes = [i32, i32, i32, i32, i32, i32, i32, sz, C.POINTER(C.c_int)]
         L.qpsk_stream_retrieve_records.argtypes = [vp, C.POINTER(C.c_void_p), u32p, C.POINTER(C.c_void_p)]
+        L.qpsk_level_host.argtypes = [vp, sz, vp]
+        L.qpsk_level_device.argtypes = [vp, sz, vp, vp]
+        L.qpsk_level_tiling.restype = None
+        L.qpsk_level_tiling.argtypes = [C.POINTER(C.c_int)]
+        L.qpsk_level_dbfs.restype = C.c_double
+        L.qpsk_level_dbfs.argtypes = [vp]
+        L.qpsk_level_sumsq_of_dbfs.restype = u64
+        L.qpsk_level_sumsq_of_dbfs.argtypes = [C.c_double]
+        L.qpsk_squelch_host.argtypes = [vp, vp, i32, i32, u64, vp, vp, vp, vp, vp]
+        L.qpsk_squelch_device.argtypes = [vp, vp, i32, i32, u64, vp, vp, vp, vp, vp, vp]
+        L.qpsk_rx_batch_records_squelch.argtypes = [vp, vp, i32, u64, vp, i32, sz, vp, vp, vp, vp, vp, vp]
+        L.qpsk_rx_batch_records_squelch_device.argtypes = [vp, vp, i32, u64, vp, i32, sz, vp, vp, vp, vp, vp, vp, vp]
         L.cnormf.restype = C.c_float
         L.cnormf.argtypes = [_CF]   # _Complex float == {float, float} in one SSE reg (SysV)
         _lib = L
@@ -239,7 +252,10 @@ SYMBOLS = ["qpsk_rx_create", "qpsk_rx_create_mode", "qpsk_rx_mode", "qpsk_rx_des
            "qpsk_bits_pack_host", "qpsk_bits_unpack_host", "qpsk_bits_pack_device", "qpsk_compact_host",
            "qpsk_compact_work_bytes", "qpsk_compact_tiling", "qpsk_compact_device", "qpsk_rx_batch_records",
            "qpsk_rx_batch_records_fmt", "qpsk_rx_batch_records_device", "qpsk_stream_create_records",
-           "qpsk_stream_retrieve_records"]
+           "qpsk_stream_retrieve_records",
+           "qpsk_level_host", "qpsk_level_device", "qpsk_level_tiling", "qpsk_level_dbfs",
+           "qpsk_level_sumsq_of_dbfs", "qpsk_squelch_host", "qpsk_squelch_device",
+           "qpsk_rx_batch_records_squelch", "qpsk_rx_batch_records_squelch_device"]
 
 
 def _check(rc: int) -> None:
@@ -646,6 +662,134 @@ def rec_from_tensor(rec, m: int | None = None) -> np.ndarray:
     return np.ascontiguousarray(a).view(REC_DTYPE).reshape(-1)
 
 
+# --- the input level meter and the squelch (include/qpsk_level.h) ---
+
+# qpsk_frame_level: 16 bytes, little endian
+LEVEL_DTYPE = np.dtype([("sumsq", "<u8"), ("sum", "<i4"), ("peak", "<u2"), ("clipped", "<u2")])
+FULL_SUMSQ = FRAME_SIZE << 30   # sumsq of a frame of -32768: 0 dBFS
+
+
+def level_tiling() -> dict:
+    """qpsk_level_tiling: the rows (frames) one workgroup of the device meter
+    takes (``rows_per_block``)."""
+    r = C.c_int(0)
+    lib().qpsk_level_tiling(C.byref(r))
+    return {"rows_per_block": r.value}
+
+
+def level_host(x) -> np.ndarray:
+    """qpsk_level_host: int16 [..., 1880] -> LEVEL_DTYPE [...], the level of
+    every frame."""
+    x = np.ascontiguousarray(x, np.int16)
+    if x.ndim < 1 or x.shape[-1] != FRAME_SIZE:
+        raise ValueError(f"expected int16 [...][{FRAME_SIZE}], got {x.shape}")
+    out = np.zeros(x.shape[:-1], LEVEL_DTYPE)
+    _check(lib().qpsk_level_host(_ptr(x), out.size, _ptr(out)))
+    return out
+
+
+def level_device(x, out=None, stream=None):
+    """qpsk_level_device: a contiguous cuda int16 tensor [..., 1880] -> an int64
+    tensor [..., 2] holding the levels (level_from_tensor gives LEVEL_DTYPE on
+    the host); enqueued on ``stream``."""
+    import torch
+    if not x.is_cuda or x.dtype != torch.int16 or x.dim() < 1 or x.shape[-1] != FRAME_SIZE or not x.is_contiguous():
+        raise ValueError(f"x must be a contiguous cuda int16 [...][{FRAME_SIZE}] tensor")
+    with torch.cuda.device(x.device), _on(stream, x.device):
+        if out is None:
+            out = torch.empty(tuple(x.shape[:-1]) + (2,), dtype=torch.int64, device=x.device)
+        _check(lib().qpsk_level_device(x.data_ptr(), x.numel() // FRAME_SIZE, out.data_ptr(),
+                                       _stream(stream, x.device)))
+    return out
+
+
+def level_from_tensor(level) -> np.ndarray:
+    """A device level tensor (int64 [..., 2]) as a LEVEL_DTYPE array [...] on the host."""
+    a = np.ascontiguousarray(level.cpu().numpy())
+    return a.view(LEVEL_DTYPE).reshape(a.shape[:-1])
+
+
+def level_dbfs(level) -> np.ndarray:
+    """qpsk_level_dbfs of every element of a LEVEL_DTYPE array (or of sumsq
+    values): float64, -inf for sumsq == 0."""
+    level = np.asarray(level)
+    if level.dtype != LEVEL_DTYPE:
+        q = np.zeros(level.shape, LEVEL_DTYPE)
+        q["sumsq"] = level
+        level = q
+    level = np.ascontiguousarray(level)
+    out = np.zeros(level.shape, np.float64)
+    flat, o = level.reshape(-1), out.reshape(-1)
+    for i in range(flat.size):
+        o[i] = lib().qpsk_level_dbfs(flat[i:i + 1].ctypes.data)
+    return out
+
+
+def sumsq_of_dbfs(db: float) -> int:
+    """qpsk_level_sumsq_of_dbfs: the smallest sumsq whose level is at least
+    ``db`` dBFS -- the ``min_sumsq`` of a squelch at that level."""
+    return int(lib().qpsk_level_sumsq_of_dbfs(float(db)))
+
+
+def _levels(a, n: int, what: str):
+    """A LEVEL_DTYPE array of n elements (or None)."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, LEVEL_DTYPE)
+    if a.size != n:
+        raise ValueError(f"{what} must have {n} levels, got {a.shape}")
+    return a
+
+
+def squelch_host(level, valid, min_sumsq: int, prev=None, bits=None, soft=None, valid_out=None, last=None) -> dict:
+    """qpsk_squelch_host: level LEVEL_DTYPE [nch][nframes] and valid uint8
+    [nch][nframes] -> {"valid" (the squelched flags), "last" (LEVEL_DTYPE
+    [nch], the levels the next call takes as ``prev``)}.  ``bits`` / ``soft``
+    (the dense arrays, C-contiguous) are written in place: the rows of frames
+    that were valid and are squelched become zero.  ``valid_out`` may be
+    ``valid`` itself and ``last`` may be ``prev``."""
+    # (an array that is contiguous and of the right type already is passed on
+    # as it is, so valid_out = valid and last = prev reach the library as one array)
+    valid = np.ascontiguousarray(valid, np.uint8)
+    if valid.ndim != 2:
+        raise ValueError(f"valid must be [nch][nframes], got {valid.shape}")
+    nch, nf = valid.shape
+    level = _levels(level, nch * nf, "level")
+    prev = _levels(prev, nch, "prev")
+    if valid_out is None:
+        valid_out = np.zeros((nch, nf), np.uint8)
+    if last is None:
+        last = np.zeros(nch, LEVEL_DTYPE)
+    for name, a, dt, shape in (("bits", bits, np.uint8, (nch, nf, NBITS)),
+                               ("soft", soft, np.float32, (nch, nf, DATA_SYMBOLS, 2)),
+                               ("valid_out", valid_out, np.uint8, (nch, nf)), ("last", last, LEVEL_DTYPE, (nch,))):
+        if a is not None and (a.dtype != dt or a.shape != shape or not a.flags.c_contiguous):
+            raise ValueError(f"{name} must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+    _check(lib().qpsk_squelch_host(_ptr(level), _ptr(prev), nch, nf, int(min_sumsq), _ptr(valid), _ptr(valid_out),
+                                   _ptr(bits), _ptr(soft), _ptr(last)))
+    return {"valid": valid_out, "last": last}
+
+
+def squelch_device(level, valid, min_sumsq: int, prev=None, bits=None, soft=None, valid_out=None, last=None,
+                   stream=None) -> dict:
+    """qpsk_squelch_device on cuda tensors: level int64 [nch][nframes][2] (as
+    level_device gives it), valid uint8 [nch][nframes], prev / last int64
+    [nch][2], bits uint8 [nch][nframes][62] and soft float32
+    [nch][nframes][31][2] (written in place).  valid_out and last are made
+    when None; enqueued on ``stream``."""
+    import torch
+    nch, nf = tuple(valid.shape)
+    dev = valid.device
+    with torch.cuda.device(dev), _on(stream, dev):
+        if valid_out is None:
+            valid_out = torch.empty((nch, nf), dtype=torch.uint8, device=dev)
+        if last is None:
+            last = torch.empty((nch, 2), dtype=torch.int64, device=dev)
+        _check(lib().qpsk_squelch_device(_ptr(level), _ptr(prev), nch, nf, int(min_sumsq), _ptr(valid),
+                                         _ptr(valid_out), _ptr(bits), _ptr(soft), _ptr(last), _stream(stream, dev)))
+    return {"valid": valid_out, "last": last}
+
+
 class Receiver:
     """A batch of ``nch`` independent receivers on one GPU (``qpsk_ctx``).
 
@@ -824,6 +968,64 @@ class Receiver:
             _check(lib().qpsk_rx_batch_records_device(self._h, _ptr(x), nf, order, cap, _ptr(rec), _ptr(rtr),
                                                       _ptr(rso), _ptr(groups), _ptr(count), _stream(stream, dev)))
         return {"rec": rec, "trace": rtr, "soft": rso, "groups": groups, "count": count}
+
+    def demod_records_squelch(self, x, min_sumsq: int, prev=None, order: int = REC_BY_CHANNEL,
+                              cap: int | None = None, trace: bool = False, soft: bool = False) -> dict:
+        """``demod_records`` behind the level meter and the squelch
+        (qpsk_rx_batch_records_squelch): frames whose own level and the level
+        of the frame in front of them are both below ``min_sumsq`` (see
+        sumsq_of_dbfs) give no record.  ``prev``: the ``"prev"`` of the
+        previous call on this stream of frames (LEVEL_DTYPE [nch]; None at its
+        start; not changed).  Returns what demod_records returns plus
+        ``"level"`` (LEVEL_DTYPE [nch][nframes]) and the new ``"prev"``."""
+        x = np.ascontiguousarray(x, dtype=np.int16)
+        if x.ndim != 3 or x.shape[0] != self.nch or x.shape[2] != FRAME_SIZE:
+            raise ValueError(f"expected int16 [{self.nch}][nframes][{FRAME_SIZE}], got {x.shape}")
+        nf = x.shape[1]
+        cap = self.nch * nf if cap is None else int(cap)
+        o = _rec_arrays(cap, trace, soft, _groups_of(order, self.nch, nf))
+        level = np.zeros((self.nch, nf), LEVEL_DTYPE)
+        # (a prev of zeros is what NULL means)
+        prev = np.zeros(self.nch, LEVEL_DTYPE) if prev is None else _levels(prev, self.nch, "prev").copy()
+        count = C.c_uint32(0)
+        _check(lib().qpsk_rx_batch_records_squelch(self._h, _ptr(x), nf, int(min_sumsq), _ptr(prev), order, cap,
+                                                   _ptr(o["rec"]), _ptr(o.get("trace")), _ptr(o.get("soft")),
+                                                   _ptr(o["groups"]), C.addressof(count), _ptr(level)))
+        r = _rec_trim(o, int(count.value), cap)
+        r["level"], r["prev"] = level, prev
+        return r
+
+    def demod_records_squelch_device(self, x, min_sumsq: int, prev=None, order: int = REC_BY_CHANNEL,
+                                     cap: int | None = None, trace: bool = False, soft: bool = False,
+                                     level: bool = True, stream=None) -> dict:
+        """``demod_records_device`` behind the meter and the squelch, all on the
+        device and asynchronous on ``stream``
+        (qpsk_rx_batch_records_squelch_device).  ``prev``: a cuda int64 [nch][2]
+        tensor that is read and then overwritten in stream order (None: the
+        start of a stream, and nothing is carried).  Returns the tensors of
+        demod_records_device plus ``"level"`` (int64 [nch][nframes][2], see
+        level_from_tensor; None with level=False) and ``"prev"``."""
+        import torch
+        if x.dtype != torch.int16 or x.dim() != 3 or x.shape[0] != self.nch \
+                or x.shape[2] != FRAME_SIZE or not x.is_contiguous() or not x.is_cuda:
+            raise ValueError("x must be a contiguous cuda int16 [nch][nframes][1880] tensor")
+        if prev is not None and (prev.dtype != torch.int64 or tuple(prev.shape) != (self.nch, 2)
+                                 or not prev.is_contiguous() or not prev.is_cuda):
+            raise ValueError("prev must be a contiguous cuda int64 [nch][2] tensor")
+        nf = x.shape[1]
+        cap = self.nch * nf if cap is None else int(cap)
+        dev = x.device
+        with torch.cuda.device(dev), _on(stream, dev):
+            rec = torch.empty((cap, 2), dtype=torch.int64, device=dev) if cap > 0 else None
+            rtr = torch.empty((cap, 4), dtype=torch.int32, device=dev) if trace else None
+            rso = torch.empty((cap, DATA_SYMBOLS, 2), dtype=torch.float32, device=dev) if soft else None
+            groups = torch.empty(_groups_of(order, self.nch, nf) + 1, dtype=torch.int32, device=dev)
+            count = torch.empty(1, dtype=torch.int32, device=dev)
+            lvl = torch.empty((self.nch, nf, 2), dtype=torch.int64, device=dev) if level else None
+            _check(lib().qpsk_rx_batch_records_squelch_device(self._h, _ptr(x), nf, int(min_sumsq), _ptr(prev), order,
+                                                              cap, _ptr(rec), _ptr(rtr), _ptr(rso), _ptr(groups),
+                                                              _ptr(count), _ptr(lvl), _stream(stream, dev)))
+        return {"rec": rec, "trace": rtr, "soft": rso, "groups": groups, "count": count, "level": lvl, "prev": prev}
 
     def sync(self) -> None:
         """Wait for the latest demod_device call; raise QpskError (QPSK_ESTALL)
