@@ -19,7 +19,7 @@
  *                                          idle channels, which the reference calls
  *                                          valid, give no record (qpsk_level.h: the
  *                                          meter, the squelch and the compaction run on
- *                                          the GPU, qpsk_rx_batch_records_squelch)
+ *                                          the GPU, qpsk_rx_batch_records_squelch_fmt)
  *   qpsk_rx_raw -f FMT in.g711 out.bin     one channel of G.711 codes, the same way
  * Output: one 496-byte record per valid frame, bits in bytes 0..61 (the
  * reference's /tmp/databits.txt format, src/qpsk.c:455-457).
@@ -78,24 +78,16 @@ static int single(const char *in, const char *out) {
 
 /* The same output files behind the squelch: the receive, the level meter, the
  * squelch at min_sumsq and the compaction on the GPU; the records that come
- * back are the frames to write, by channel.  G.711 codes are expanded here
- * first (the record call with squelch takes int16). */
+ * back are the frames to write, by channel.  G.711 codes cross PCIe as they
+ * are here too: the conversion on the GPU takes the levels in its own pass. */
 static int squelched(qpsk_ctx *ctx, int nch, int nf, const char *in, int fmt, uint64_t min_sumsq,
                      const char *prefix) {
     const size_t cf = (size_t)nch * nf;
-    int16_t *x = NULL;
-    if (fmt != QPSK_IN_S16) {
-        x = malloc(sizeof(int16_t) * cf * FRAME_SIZE);
-        const int err = qpsk_input_convert_host(fmt | QPSK_IN_PLANAR, in, 0, nch, nf, x, 1);
-        if (err) {
-            fprintf(stderr, "qpsk: %s\n", qpsk_strerror(err));
-            return 3;
-        }
-    }
     qpsk_frame_rec *recs = malloc(sizeof *recs * cf);
     uint32_t *groups = malloc(sizeof *groups * ((size_t)nch + 1)), count = 0;
-    const int err = qpsk_rx_batch_records_squelch(ctx, x ? x : (const int16_t *)in, nf, min_sumsq, NULL,
-                                                  QPSK_REC_BY_CHANNEL, cf, recs, NULL, NULL, groups, &count, NULL);
+    const int err = qpsk_rx_batch_records_squelch_fmt(ctx, in, fmt | QPSK_IN_PLANAR, 0, nf, min_sumsq, NULL,
+                                                      QPSK_REC_BY_CHANNEL, cf, recs, NULL, NULL, groups, &count,
+                                                      NULL);
     if (err) {
         fprintf(stderr, "qpsk: %s\n", qpsk_strerror(err));
         return 3;
@@ -113,7 +105,7 @@ static int squelched(qpsk_ctx *ctx, int nch, int nf, const char *in, int fmt, ui
         }
         fclose(fo);
     }
-    free(x), free(recs), free(groups);
+    free(recs), free(groups);
     return 0;
 }
 

@@ -10,13 +10,18 @@
  *   qpsk_rx_stream [-f FRAMES_PER_CHUNK] [-f FMT] in1.raw [in2.raw ...] -o PREFIX
  *   qpsk_rx_stream [-f FRAMES_PER_CHUNK] [-f FMT] -i NCH trunk.raw -o PREFIX
  *   qpsk_rx_stream ... -p FILE      (in place of -o PREFIX)
+ *   qpsk_rx_stream -q DBFS ... -p FILE
  *
  * -p FILE: one file of 16-byte records (qpsk_frame_rec, include/qpsk_compact.h:
  * channel, frame, the 62 bits in one word) of all channels in time order,
  * instead of the per-channel files: the stream is one of records in by-frame
  * order (qpsk_stream_create_records), only the valid frames cross PCIe, and a
  * record's frame is its position in the whole stream (the chunk's first frame
- * added).
+ * added).  -q DBFS (with -p FILE): the records pass the squelch at that input
+ * level, in dB relative to full scale (e.g. -60): frames of idle channels,
+ * which the reference calls valid, give no record, and the file holds only the
+ * records the squelch keeps (qpsk_stream_create_records_squelch,
+ * include/qpsk_level.h; the levels are carried from chunk to chunk).
  *
  * FMT = s16 (default), alaw or ulaw: the files hold 8-bit G.711 codes, which go
  * into the pinned slots and over PCIe as they are and are expanded on the GPU
@@ -35,6 +40,7 @@
 #include "qpsk_compact.h"
 #include "qpsk_input.h"
 #include "qpsk_internal.h"
+#include "qpsk_level.h"
 #include "qpsk_stream.h"
 
 static void drain(qpsk_stream *s, int nch, int frames, int nf_chunk, FILE **out, uint8_t *rec) {
@@ -70,15 +76,17 @@ static void drain_records(qpsk_stream *s, int nf_chunk, long first_frame, FILE *
 }
 
 static void usage(const char *argv0) {
-    fprintf(stderr, "usage: %s [-f FRAMES_PER_CHUNK] [-f s16|alaw|ulaw] (in1.raw [in2.raw ...] | -i NCH trunk.raw) "
-                    "(-o PREFIX | -p FILE)\n", argv0);
+    fprintf(stderr, "usage: %s [-f FRAMES_PER_CHUNK] [-f s16|alaw|ulaw] [-q DBFS] (in1.raw [in2.raw ...] | "
+                    "-i NCH trunk.raw) (-o PREFIX | -p FILE)   (-q needs -p)\n", argv0);
 }
 
 int main(int argc, char **argv) {
     int frames = 8, a = 1, fmt = QPSK_IN_S16, trunk = 0;
-    while (a + 1 < argc && (!strcmp(argv[a], "-f") || !strcmp(argv[a], "-i"))) {
+    const char *squelch_db = NULL;
+    while (a + 1 < argc && (!strcmp(argv[a], "-f") || !strcmp(argv[a], "-i") || !strcmp(argv[a], "-q"))) {
         const char *v = argv[a + 1];
         if (!strcmp(argv[a], "-i")) trunk = atoi(v);
+        else if (!strcmp(argv[a], "-q")) squelch_db = v;
         else if (!strcmp(v, "s16")) fmt = QPSK_IN_S16;
         else if (!strcmp(v, "alaw")) fmt = QPSK_IN_ALAW;
         else if (!strcmp(v, "ulaw")) fmt = QPSK_IN_ULAW;
@@ -86,7 +94,8 @@ int main(int argc, char **argv) {
         a += 2;
     }
     const int packed = argc >= 2 && !strcmp(argv[argc - 2], "-p");
-    if (argc - a < 3 || (!packed && strcmp(argv[argc - 2], "-o")) || frames < 1 || trunk < 0 || (trunk && argc - a != 3)) {
+    if (argc - a < 3 || (!packed && strcmp(argv[argc - 2], "-o")) || frames < 1 || trunk < 0 ||
+        (trunk && argc - a != 3) || (squelch_db && !packed)) {
         usage(argv[0]);
         return 2;
     }
@@ -108,9 +117,13 @@ int main(int argc, char **argv) {
     const int nslot = 3;
     int err;
     /* (planar int16 is the plain stream: qpsk_stream_create) */
-    qpsk_stream *s = packed ? qpsk_stream_create_records(0, nch, frames, nslot, QPSK_MODE_REFERENCE, fmt,
-                                                         QPSK_REC_BY_FRAME, (size_t)nch * (size_t)frames, &err)
-                            : qpsk_stream_create_fmt(0, nch, frames, nslot, QPSK_MODE_REFERENCE, fmt, &err);
+    const size_t cap = (size_t)nch * (size_t)frames;
+    qpsk_stream *s = squelch_db ? qpsk_stream_create_records_squelch(0, nch, frames, nslot, QPSK_MODE_REFERENCE, fmt,
+                                                                     QPSK_REC_BY_FRAME, cap,
+                                                                     qpsk_level_sumsq_of_dbfs(atof(squelch_db)), &err)
+                   : packed     ? qpsk_stream_create_records(0, nch, frames, nslot, QPSK_MODE_REFERENCE, fmt,
+                                                             QPSK_REC_BY_FRAME, cap, &err)
+                                : qpsk_stream_create_fmt(0, nch, frames, nslot, QPSK_MODE_REFERENCE, fmt, &err);
     if (!s) {
         fprintf(stderr, "qpsk: %s\n", qpsk_strerror(err));
         return 3;

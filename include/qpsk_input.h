@@ -36,6 +36,7 @@
 #include <stdint.h>
 
 #include "qpsk_batch.h"
+#include "qpsk_level.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -67,6 +68,42 @@ int qpsk_input_convert_host(int fmt, const void *src, long ld, int nch, int nfra
  * not overlap d_out.  Both are device pointers of the current device. */
 int qpsk_input_convert_device(int fmt, const void *d_src, long ld, int nch, int nframes,
                               int16_t *d_out, void *stream);
+
+/*
+ * The conversion with the level meter (qpsk_level.h) in its pass: d_out is
+ * exactly what qpsk_input_convert_device writes, and level[c * nframes + f] is
+ * exactly qpsk_level_host of row (c, f) of that output -- integer arithmetic,
+ * bit for bit.  The samples are metered while the conversion has them in
+ * registers: the source is read once, d_out is written once and is not read.
+ *
+ *   planar G.711   one launch: a wave converts one frame and stores its level.
+ *                  No work area (qpsk_input_level_work_bytes is 0).
+ *   interleaved    the tiled conversion stores one partial level per channel
+ *                  and per part of a frame inside a tile of 128 samples to
+ *                  d_work; a second small launch in stream order folds the 15
+ *                  or 16 partials of a frame.  16 partials of 16 bytes a
+ *                  channel-frame.
+ *   planar int16   has no conversion pass: the copy, then qpsk_level_device on
+ *                  d_out in stream order.  No work area.
+ *
+ * Every element of d_level is written once, with a plain store, into memory
+ * the caller need not have cleared; there are no atomics, and no workgroup
+ * waits for another.  d_work (at least qpsk_input_level_work_bytes bytes,
+ * 16-byte aligned; may be NULL where that is 0) holds nothing between calls.
+ *
+ * Errors: those of qpsk_input_convert_device, and QPSK_EINVAL for a NULL
+ * d_level, a d_level that is not 8-byte aligned, a work area that is too small
+ * (or NULL where one is needed) or not 16-byte aligned; all checked before any
+ * HIP call.  nframes == 0 does nothing and is QPSK_OK.
+ */
+size_t qpsk_input_level_work_bytes(int fmt, int nch, int nframes, long ld);
+int qpsk_input_convert_level_device(int fmt, const void *d_src, long ld, int nch, int nframes,
+                                    int16_t *d_out, qpsk_frame_level *d_level,
+                                    void *d_work, size_t work_bytes, void *stream);
+/* The host twin: qpsk_input_convert_host followed by qpsk_level_host, and what
+ * every GPU result is compared with. */
+int qpsk_input_convert_level_host(int fmt, const void *src, long ld, int nch, int nframes,
+                                  int16_t *out, qpsk_frame_level *level, int nthreads);
 
 /* qpsk_rx_batch() for input in format `fmt`: copies the source block as it is
  * over PCIe, converts it on the device and receives.  Returns what

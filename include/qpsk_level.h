@@ -133,6 +133,44 @@ int qpsk_rx_batch_records_squelch_device(qpsk_ctx *ctx, const int16_t *d_in, int
                                          uint32_t *d_groups, uint32_t *d_count, qpsk_frame_level *d_level,
                                          void *stream);
 
+/*
+ * The same two calls for input in format `fmt` (qpsk_input.h), taken as
+ * qpsk_rx_batch_records_fmt and qpsk_rx_batch_device_fmt take it: the host
+ * form copies the source block over PCIe as it is.  QPSK_IN_S16 |
+ * QPSK_IN_PLANAR forwards to the calls above.  For every other format the
+ * levels are taken by the conversion itself, while it has the samples in
+ * registers (qpsk_input_convert_level_device): the meter does not read the
+ * converted block again, and `level` is the level of the decoded samples.
+ */
+int qpsk_rx_batch_records_squelch_fmt(qpsk_ctx *ctx, const void *in, int fmt, long ld, int nframes,
+                                      uint64_t min_sumsq, qpsk_frame_level *prev_io, int order, size_t cap,
+                                      qpsk_frame_rec *rec, int32_t *rec_trace, float *rec_soft, uint32_t *groups,
+                                      uint32_t *count, qpsk_frame_level *level);
+int qpsk_rx_batch_records_squelch_device_fmt(qpsk_ctx *ctx, const void *d_in, int fmt, long ld, int nframes,
+                                             uint64_t min_sumsq, qpsk_frame_level *d_prev_io, int order, size_t cap,
+                                             qpsk_frame_rec *d_rec, int32_t *d_rec_trace, float *d_rec_soft,
+                                             uint32_t *d_groups, uint32_t *d_count, qpsk_frame_level *d_level,
+                                             void *stream);
+
+/*
+ * Record streams with squelch: qpsk_stream_create_records (qpsk_compact.h)
+ * whose chunks pass the meter and the squelch between the receive and the
+ * compaction.  The stream owns the carried levels, a device array [nch]: zero
+ * at creation -- the start of a stream, where the receiver's history is zeros
+ * -- and read as `prev` and written as `last` by each chunk in submit order.
+ * A chunk's levels come from the conversion's pass for converted formats and
+ * from qpsk_level_device on the slot's input for planar int16.  They stay on
+ * the device unless `level` (nullable) is given: then they are copied to the
+ * slot's pinned memory on retrieval, as the records are, [nch][frames], good
+ * until the slot is acquired again.  qpsk_stream_retrieve_records works on
+ * such a stream as on any record stream; qpsk_stream_retrieve is QPSK_EINVAL.
+ * With a non-NULL `level` on a record stream without squelch: QPSK_EINVAL.
+ */
+qpsk_stream *qpsk_stream_create_records_squelch(int device, int nch, int frames, int nslot, int mode, int fmt,
+                                                int order, size_t cap, uint64_t min_sumsq, int *err);
+int qpsk_stream_retrieve_records_squelch(qpsk_stream *s, const qpsk_frame_rec **rec, uint32_t *count,
+                                         const uint32_t **groups, const qpsk_frame_level **level);
+
 #ifdef __cplusplus
 }
 #endif

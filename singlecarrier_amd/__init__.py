@@ -222,6 +222,21 @@ def lib():
         L.qpsk_squelch_device.argtypes = [vp, vp, i32, i32, u64, vp, vp, vp, vp, vp, vp]
         L.qpsk_rx_batch_records_squelch.argtypes = [vp, vp, i32, u64, vp, i32, sz, vp, vp, vp, vp, vp, vp]
         L.qpsk_rx_batch_records_squelch_device.argtypes = [vp, vp, i32, u64, vp, i32, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.qpsk_input_level_work_bytes.restype = sz
+        L.qpsk_input_level_work_bytes.argtypes = [i32, i32, i32, C.c_long]
+        L.qpsk_input_convert_level_host.argtypes = [i32, vp, C.c_long, i32, i32, vp, vp, i32]
+        L.qpsk_input_convert_level_device.argtypes = [i32, vp, C.c_long, i32, i32, vp, vp, vp, sz, vp]
+        L.qpsk_input_convert_level_device_grid.argtypes = [i32, vp, C.c_long, i32, i32, vp, vp, vp, sz, vp, i32,
+                                                           C.c_uint]
+        L.qpsk_rx_batch_records_squelch_fmt.argtypes = [vp, vp, i32, C.c_long, i32, u64, vp, i32, sz, vp, vp, vp, vp,
+                                                        vp, vp]
+        L.qpsk_rx_batch_records_squelch_device_fmt.argtypes = [vp, vp, i32, C.c_long, i32, u64, vp, i32, sz, vp, vp,
+                                                               vp, vp, vp, vp, vp]
+        L.qpsk_stream_create_records_squelch.restype = vp
+        L.qpsk_stream_create_records_squelch.argtypes = [i32, i32, i32, i32, i32, i32, i32, sz, u64,
+                                                         C.POINTER(C.c_int)]
+        L.qpsk_stream_retrieve_records_squelch.argtypes = [vp, C.POINTER(C.c_void_p), u32p, C.POINTER(C.c_void_p),
+                                                           C.POINTER(C.c_void_p)]
         L.cnormf.restype = C.c_float
         L.cnormf.argtypes = [_CF]   # _Complex float == {float, float} in one SSE reg (SysV)
         _lib = L
@@ -255,7 +270,10 @@ SYMBOLS = ["qpsk_rx_create", "qpsk_rx_create_mode", "qpsk_rx_mode", "qpsk_rx_des
            "qpsk_stream_retrieve_records",
            "qpsk_level_host", "qpsk_level_device", "qpsk_level_tiling", "qpsk_level_dbfs",
            "qpsk_level_sumsq_of_dbfs", "qpsk_squelch_host", "qpsk_squelch_device",
-           "qpsk_rx_batch_records_squelch", "qpsk_rx_batch_records_squelch_device"]
+           "qpsk_rx_batch_records_squelch", "qpsk_rx_batch_records_squelch_device",
+           "qpsk_input_level_work_bytes", "qpsk_input_convert_level_host", "qpsk_input_convert_level_device",
+           "qpsk_rx_batch_records_squelch_fmt", "qpsk_rx_batch_records_squelch_device_fmt",
+           "qpsk_stream_create_records_squelch", "qpsk_stream_retrieve_records_squelch"]
 
 
 def _check(rc: int) -> None:
@@ -790,6 +808,53 @@ def squelch_device(level, valid, min_sumsq: int, prev=None, bits=None, soft=None
     return {"valid": valid_out, "last": last}
 
 
+def input_level_work_bytes(fmt: int, nch: int, nframes: int, ld: int = 0) -> int:
+    """qpsk_input_level_work_bytes: bytes of input_convert_level_device's work
+    area (0 for a planar block, for no frames and for refused arguments)."""
+    return int(lib().qpsk_input_level_work_bytes(fmt, nch, nframes, ld))
+
+
+def input_convert_level_host(x, fmt: int, nch: int, threads: int = 0):
+    """qpsk_input_convert_level_host: input_convert_host and level_host of its
+    output, as (int16 [nch][nframes][1880], LEVEL_DTYPE [nch][nframes])."""
+    _fmt_check(fmt, nch)
+    x, nf, ld = _np_block(x, fmt, nch)
+    out = np.empty((nch, nf, FRAME_SIZE), np.int16)
+    level = np.zeros((nch, nf), LEVEL_DTYPE)
+    _check(lib().qpsk_input_convert_level_host(fmt, _ptr(x), ld, nch, nf, _ptr(out), _ptr(level), _threads(threads)))
+    return out, level
+
+
+def input_convert_level_device(x, fmt: int, nch: int, out=None, level=None, work=None, stream=None):
+    """qpsk_input_convert_level_device: input_convert_device that also takes
+    the level of every frame in the same pass.  Returns (out, level): int16
+    [nch][nframes][1880] and int64 [nch][nframes][2] (see level_from_tensor)
+    on the source's device.  ``work`` (a cuda uint8 tensor of at least
+    input_level_work_bytes) is made when None; enqueued on ``stream``."""
+    import torch
+    _fmt_check(fmt, nch)
+    nf, ld = _torch_block(x, fmt, nch)
+    dev = x.device
+    if out is not None and (out.dtype != torch.int16 or tuple(out.shape) != (nch, nf, FRAME_SIZE)
+                            or not out.is_contiguous() or not out.is_cuda):
+        raise ValueError(f"out must be a contiguous cuda int16 [{nch}][{nf}][{FRAME_SIZE}] tensor")
+    if level is not None and (level.dtype != torch.int64 or tuple(level.shape) != (nch, nf, 2)
+                              or not level.is_contiguous() or not level.is_cuda):
+        raise ValueError(f"level must be a contiguous cuda int64 [{nch}][{nf}][2] tensor")
+    need = input_level_work_bytes(fmt, nch, nf, ld)
+    with torch.cuda.device(dev), _on(stream, dev):
+        if out is None:
+            out = torch.empty((nch, nf, FRAME_SIZE), dtype=torch.int16, device=dev)
+        if level is None:
+            level = torch.empty((nch, nf, 2), dtype=torch.int64, device=dev)
+        if work is None and need:
+            work = torch.empty(need, dtype=torch.uint8, device=dev)
+        _check(lib().qpsk_input_convert_level_device(fmt, x.data_ptr(), ld, nch, nf, out.data_ptr(), level.data_ptr(),
+                                                     _ptr(work), work.numel() if work is not None else 0,
+                                                     _stream(stream, dev)))
+    return out, level
+
+
 class Receiver:
     """A batch of ``nch`` independent receivers on one GPU (``qpsk_ctx``).
 
@@ -1027,6 +1092,53 @@ class Receiver:
                                                               _ptr(count), _ptr(lvl), _stream(stream, dev)))
         return {"rec": rec, "trace": rtr, "soft": rso, "groups": groups, "count": count, "level": lvl, "prev": prev}
 
+    def demod_records_squelch_fmt(self, x, fmt: int, min_sumsq: int, prev=None, order: int = REC_BY_CHANNEL,
+                                  cap: int | None = None, trace: bool = False, soft: bool = False) -> dict:
+        """``demod_records_squelch`` for a host source block in format ``fmt``
+        (as demod_fmt takes it; qpsk_rx_batch_records_squelch_fmt).  The block
+        crosses PCIe as it is; ``"level"`` is the level of the decoded samples,
+        taken by the conversion's own pass."""
+        _fmt_check(fmt, self.nch)
+        x, nf, ld = _np_block(x, fmt, self.nch)
+        cap = self.nch * nf if cap is None else int(cap)
+        o = _rec_arrays(cap, trace, soft, _groups_of(order, self.nch, nf))
+        level = np.zeros((self.nch, nf), LEVEL_DTYPE)
+        prev = np.zeros(self.nch, LEVEL_DTYPE) if prev is None else _levels(prev, self.nch, "prev").copy()
+        count = C.c_uint32(0)
+        _check(lib().qpsk_rx_batch_records_squelch_fmt(self._h, _ptr(x), fmt, ld, nf, int(min_sumsq), _ptr(prev),
+                                                       order, cap, _ptr(o["rec"]), _ptr(o.get("trace")),
+                                                       _ptr(o.get("soft")), _ptr(o["groups"]), C.addressof(count),
+                                                       _ptr(level)))
+        r = _rec_trim(o, int(count.value), cap)
+        r["level"], r["prev"] = level, prev
+        return r
+
+    def demod_records_squelch_device_fmt(self, x, fmt: int, min_sumsq: int, prev=None, order: int = REC_BY_CHANNEL,
+                                         cap: int | None = None, trace: bool = False, soft: bool = False,
+                                         level: bool = True, stream=None) -> dict:
+        """``demod_records_squelch_device`` for a cuda source block in format
+        ``fmt`` (layouts as demod_fmt; qpsk_rx_batch_records_squelch_device_fmt)."""
+        import torch
+        _fmt_check(fmt, self.nch)
+        nf, ld = _torch_block(x, fmt, self.nch)
+        if prev is not None and (prev.dtype != torch.int64 or tuple(prev.shape) != (self.nch, 2)
+                                 or not prev.is_contiguous() or not prev.is_cuda):
+            raise ValueError("prev must be a contiguous cuda int64 [nch][2] tensor")
+        cap = self.nch * nf if cap is None else int(cap)
+        dev = x.device
+        with torch.cuda.device(dev), _on(stream, dev):
+            rec = torch.empty((cap, 2), dtype=torch.int64, device=dev) if cap > 0 else None
+            rtr = torch.empty((cap, 4), dtype=torch.int32, device=dev) if trace else None
+            rso = torch.empty((cap, DATA_SYMBOLS, 2), dtype=torch.float32, device=dev) if soft else None
+            groups = torch.empty(_groups_of(order, self.nch, nf) + 1, dtype=torch.int32, device=dev)
+            count = torch.empty(1, dtype=torch.int32, device=dev)
+            lvl = torch.empty((self.nch, nf, 2), dtype=torch.int64, device=dev) if level else None
+            _check(lib().qpsk_rx_batch_records_squelch_device_fmt(self._h, x.data_ptr(), fmt, ld, nf, int(min_sumsq),
+                                                                  _ptr(prev), order, cap, _ptr(rec), _ptr(rtr),
+                                                                  _ptr(rso), _ptr(groups), _ptr(count), _ptr(lvl),
+                                                                  _stream(stream, dev)))
+        return {"rec": rec, "trace": rtr, "soft": rso, "groups": groups, "count": count, "level": lvl, "prev": prev}
+
     def sync(self) -> None:
         """Wait for the latest demod_device call; raise QpskError (QPSK_ESTALL)
         if any call since the previous check failed on the device."""
@@ -1189,15 +1301,25 @@ class Stream:
     planar int16 (IN_*) the chunks are source blocks in that format, filled
     through ``acquire_raw()`` and converted on the GPU.  With ``records=True``
     the chunks come back through ``retrieve_records()`` as the list of their
-    valid frames in ``order``, at most ``cap`` a chunk (include/qpsk_compact.h)."""
+    valid frames in ``order``, at most ``cap`` a chunk (include/qpsk_compact.h).
+    With ``min_sumsq`` (and ``records=True``) the records pass the level meter
+    and the squelch (include/qpsk_level.h): the stream carries each channel's
+    last level from chunk to chunk, from zero at its start, and
+    ``retrieve_records(levels=True)`` also gives the chunk's levels."""
 
     def __init__(self, nch: int, frames: int, nslot: int = 3, device: int = 0,
                  mode: int = MODE_REFERENCE, fmt: int = IN_S16 | IN_PLANAR, records: bool = False,
-                 order: int = REC_BY_CHANNEL, cap: int | None = None):
+                 order: int = REC_BY_CHANNEL, cap: int | None = None, min_sumsq: int | None = None):
         err = C.c_int(0)
         self.records, self.order = bool(records), order
         self.cap = min(nch * frames, nch * frames if cap is None else int(cap))
-        if records:
+        self.squelch = min_sumsq is not None
+        if self.squelch and not records:
+            raise ValueError("min_sumsq needs records=True")
+        if self.squelch:
+            self._h = lib().qpsk_stream_create_records_squelch(device, nch, frames, nslot, mode, fmt, order, self.cap,
+                                                               int(min_sumsq), C.byref(err))
+        elif records:
             self._h = lib().qpsk_stream_create_records(device, nch, frames, nslot, mode, fmt, order, self.cap,
                                                        C.byref(err))
         elif fmt == IN_S16 | IN_PLANAR:
@@ -1258,17 +1380,28 @@ class Stream:
         valid = valid.reshape(self.nch, self.frames)
         return (bits.copy(), valid.copy()) if copy else (bits, valid)
 
-    def retrieve_records(self, copy: bool = True) -> dict:
+    def retrieve_records(self, copy: bool = True, levels: bool = False) -> dict:
         """{"rec" (REC_DTYPE, min(count, cap) of them), "count", "groups"} of
-        the oldest chunk of a ``records=True`` stream."""
-        r, g, count = C.c_void_p(), C.c_void_p(), C.c_uint32(0)
-        _check(lib().qpsk_stream_retrieve_records(self._h, C.byref(r), C.byref(count), C.byref(g)))
+        the oldest chunk of a ``records=True`` stream; with ``levels=True`` (a
+        stream with ``min_sumsq``) also ``"level"``, LEVEL_DTYPE [nch][frames]."""
+        r, g, count, lv = C.c_void_p(), C.c_void_p(), C.c_uint32(0), C.c_void_p()
+        if levels:
+            _check(lib().qpsk_stream_retrieve_records_squelch(self._h, C.byref(r), C.byref(count), C.byref(g),
+                                                              C.byref(lv)))
+        else:
+            _check(lib().qpsk_stream_retrieve_records(self._h, C.byref(r), C.byref(count), C.byref(g)))
         m = min(int(count.value), self.cap)
         ng = _groups_of(self.order, self.nch, self.frames) + 1
         rec = np.frombuffer((C.c_uint8 * (16 * m)).from_address(r.value), REC_DTYPE) if m else np.zeros(0, REC_DTYPE)
         groups = np.frombuffer((C.c_uint32 * ng).from_address(g.value), np.uint32)
-        return {"rec": rec.copy() if copy else rec, "count": int(count.value),
-                "groups": groups.copy() if copy else groups}
+        out = {"rec": rec.copy() if copy else rec, "count": int(count.value),
+               "groups": groups.copy() if copy else groups}
+        if levels:
+            cf = self.nch * self.frames
+            level = np.frombuffer((C.c_uint8 * (16 * cf)).from_address(lv.value), LEVEL_DTYPE)
+            level = level.reshape(self.nch, self.frames)
+            out["level"] = level.copy() if copy else level
+        return out
 
 
 def cnormf(val: complex) -> float:

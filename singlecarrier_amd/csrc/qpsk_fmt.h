@@ -88,6 +88,19 @@ QPSK_FMT_FN size_t qpsk_input_elems(int fmt, int nch, int nframes, long ld) {
                                                        : (size_t)nch * T;
 }
 
+/* The time tiles of the interleaved conversion (128 samples, qpsk_fmt_dev.h) a
+ * frame can span: 1880 samples from an offset of up to 120 end inside the 16th */
+#define QPSK_IN_LEVEL_FRAME_TILES 16
+
+/* bytes of qpsk_input_convert_level_device's work area: the partial levels of
+ * an interleaved block, [nframes][16][nch] of 16 bytes; 0 for a planar block,
+ * for nframes == 0 and for arguments the conversions refuse */
+QPSK_FMT_FN size_t qpsk_input_level_work(int fmt, int nch, int nframes, long ld) {
+    if (qpsk_input_check(fmt, nch, nframes, ld) != QPSK_OK) return 0;
+    if (QPSK_FMT_LAYOUT(fmt) != QPSK_IN_INTERLEAVED) return 0;
+    return (size_t)nframes * QPSK_IN_LEVEL_FRAME_TILES * (size_t)nch * sizeof(qpsk_frame_level);
+}
+
 /* Output: the same for a block of nch channels x n samples */
 QPSK_FMT_FN int qpsk_output_check(int fmt, int nch, long n, long src_ld, long ld) {
     if (qpsk_fmt_esize(fmt) == 0 || nch < 1 || n < 0 || src_ld < n) return QPSK_EINVAL;

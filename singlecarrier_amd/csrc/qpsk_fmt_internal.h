@@ -4,7 +4,10 @@
  * through the library's symbol table. */
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
+
+#include "qpsk_level.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -23,6 +26,15 @@ enum {
 /* qpsk_input_convert_device with the decoder named */
 int qpsk_input_convert_device_dec(int fmt, const void *d_src, long ld, int nch, int nframes,
                                   int16_t *d_out, void *stream, int dec);
+
+/* qpsk_input_convert_level_device with the decoder named and the grid capped
+ * at grid_cap workgroups (0: the launch's own limit).  With a cap below the
+ * tiles (interleaved) or the groups of 4 rows (planar) of a small block one
+ * workgroup takes several, which the product reaches only past 2^20 of them:
+ * the accumulators of that loop must start anew each time. */
+int qpsk_input_convert_level_device_grid(int fmt, const void *d_src, long ld, int nch, int nframes,
+                                         int16_t *d_out, qpsk_frame_level *d_level, void *d_work, size_t work_bytes,
+                                         void *stream, int dec, unsigned grid_cap);
 
 /* qpsk_output_convert_device that also reports which kernel it enqueued:
  * *width (nullable) is the bytes of a lane's global store in the interleaved

@@ -20,6 +20,14 @@
 //                       stores 128-byte runs of 8 channels.  LDS banking of both
 //                       sides: DESIGN.md (f2).
 //
+// qpsk_input_convert_level_device is the same conversion with the level meter
+// (include/qpsk_level.h) in its pass, on the samples a lane has in registers:
+// interleaved_kernel with one more argument, which keeps a level per lane in
+// LDS, folds them per channel and tile part and stores partial levels that
+// fold_kernel, a second launch, sums per frame; and planar_level_kernel, a
+// wave a frame, which needs no partials.  The kernels without the level are
+// the code they were (profiles/meter_fused_disasm.txt).
+//
 // G.711 is decoded either with the integer expansion (qpsk_fmt.h) or
 // through a 256-entry table in LDS that each block makes with it;
 // qpsk_input_convert_device_dec names one, profiles/input_bench.py times both,
@@ -37,6 +45,8 @@
 #include "qpsk_consts.h"
 #include "qpsk_fmt_dev.h"
 #include "qpsk_herr.h"
+#include "qpsk_level.h"
+#include "qpsk_level_dev.h"
 #include "qpsk_rx_internal.h"
 #include "qpsk_rx_plan.h"
 #include "qpsk_stream.h"
@@ -44,6 +54,7 @@
 namespace {
 
 using namespace qfmt;
+using namespace qlevel;   // LevelWords, Acc, take2, merge, wave_reduce, pack, unpack
 
 // the block's decode table (QPSK_IN_DEC_TABLE), ready after the next __syncthreads()
 template <int ENC, int DEC>
@@ -100,11 +111,47 @@ __global__ __launch_bounds__(kBlock) void planar_kernel(const uint8_t* __restric
     }
 }
 
-template <int ENC, int W, int DEC>
+// the level of a lane's 8 samples as the tile keeps it in LDS: one 16-byte word
+__device__ __forceinline__ uint4 lds_pack(const Acc& a) {
+    return make_uint4((unsigned)a.sumsq, (unsigned)(a.sumsq >> 32), (unsigned)a.sum, a.peak | a.clipped << 16);
+}
+
+__device__ __forceinline__ Acc lds_unpack(const uint4& w) {
+    Acc a;
+    a.sumsq = (unsigned long long)w.x | (unsigned long long)w.y << 32;
+    a.sum = (int)w.z;
+    a.peak = w.w & 0xffffu;
+    a.clipped = w.w >> 16;
+    return a;
+}
+
+// lv[tq][c] of a tile with levels; a tile without them has no such array
+template <bool LVL> struct TileLevels {
+    static __device__ __forceinline__ uint4* get() { return nullptr; }
+};
+template <> struct TileLevels<true> {
+    static __device__ __forceinline__ uint4* get() {
+        __shared__ __attribute__((aligned(16))) uint4 lv[(kTT / 8) * kTC];
+        return lv;
+    }
+};
+
+// interleaved_kernel with one more argument, LevelWords* part (LVL): the
+// store phase also takes the level of each lane's 8 samples (a group of 8 lies
+// inside one frame: 1880 = 8 * 235) into lv[tq][c]; behind the tile's last
+// barrier two waves fold them per channel, one for the part of the tile in
+// front of the frame boundary it holds and one for the part behind it (at most
+// one boundary in 128 samples, at a multiple of 8), and store the two partial
+// levels to part[frame][tile of the frame][channel].  The accumulators start
+// anew with every tile of the grid-stride loop.  LDS: ds_write_b128 goes by
+// groups of 8 lanes, which here write the 128 contiguous bytes of 8 channels,
+// and the fold reads 16 bytes a lane along the channels: both free of conflicts.
+template <int ENC, int W, int DEC, class... Part>
 __global__ __launch_bounds__(kBlock) void interleaved_kernel(const uint8_t* __restrict__ src, size_t ld,
                                                              unsigned nch, size_t T,
                                                              int16_t* __restrict__ out, unsigned ctiles,
-                                                             size_t ntiles) {
+                                                             size_t ntiles, Part... part_arg) {
+    constexpr bool LVL = sizeof...(Part) != 0;   // one more argument: LevelWords* part
     constexpr int ES = ENC == QPSK_IN_S16 ? 2 : 1;   // bytes of an element
     constexpr int RS = kTC * ES + 4;                 // bytes of a tile row in LDS: one dword of padding
     constexpr int LPR = kTC * ES / W;                // lanes that load a row
@@ -115,6 +162,7 @@ __global__ __launch_bounds__(kBlock) void interleaved_kernel(const uint8_t* __re
     static_assert(W >= ES && LPR >= 1 && RPP <= kTT && NP * RPP == kTT, "tile shape");
     __shared__ __attribute__((aligned(16))) uint8_t raw[kTT * RS];
     __shared__ int16_t tab[256];
+    uint4* const lv = TileLevels<LVL>::get();
     fill_table<ENC, DEC>(tab);
     const unsigned k = threadIdx.x % LPR, r0 = threadIdx.x / LPR;
     for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -169,11 +217,123 @@ __global__ __launch_bounds__(kBlock) void interleaved_kernel(const uint8_t* __re
                     const unsigned code = ES == 1 ? raw[b] : *reinterpret_cast<const uint16_t*>(raw + b);
                     x[i] = decode<ENC, DEC>(code, tab);
                 }
-                *reinterpret_cast<uint4*>(out + (size_t)(c0 + c) * T + t) =
-                    make_uint4(x[0] | x[1] << 16, x[2] | x[3] << 16, x[4] | x[5] << 16, x[6] | x[7] << 16);
+                const uint4 o = make_uint4(x[0] | x[1] << 16, x[2] | x[3] << 16, x[4] | x[5] << 16, x[6] | x[7] << 16);
+                *reinterpret_cast<uint4*>(out + (size_t)(c0 + c) * T + t) = o;
+                if constexpr (LVL) {
+                    Acc a;
+                    take2(a, (int)o.x);
+                    take2(a, (int)o.y);
+                    take2(a, (int)o.z);
+                    take2(a, (int)o.w);
+                    lv[tq * kTC + c] = lds_pack(a);
+                }
+            } else if constexpr (LVL) {
+                lv[tq * kTC + c] = make_uint4(0, 0, 0, 0);   // nothing there: adds nothing to any field
             }
         }
         __syncthreads();   // the tile is rewritten by the next round
+        if constexpr (LVL) {
+            // (lv is written again only behind the next tile's first barrier)
+            if (threadIdx.x < 2 * kTC) {
+                const unsigned c = threadIdx.x % kTC, behind = threadIdx.x / kTC;   // a wave each
+                const size_t f0 = t0 / QK_FRAME, edge = (f0 + 1) * QK_FRAME;        // the frame of the tile's first sample
+                const unsigned b = edge - t0 < (size_t)kTT ? (unsigned)(edge - t0) / 8 : kTT / 8;
+                const unsigned lo = behind ? b : 0, hi = behind ? kTT / 8 : b;
+                if (c0 + c < nch && lo < hi && t0 + lo * 8 < T) {
+                    Acc a;
+                    for (unsigned tq = lo; tq < hi; tq++) merge(a, lds_unpack(lv[tq * kTC + c]));
+                    const size_t f = f0 + behind, first = f * QK_FRAME / kTT;   // the first tile of frame f
+                    LevelWords* const part = (part_arg, ...);
+                    part[((f * QPSK_IN_LEVEL_FRAME_TILES + (t0 / kTT - first)) * nch) + c0 + c] = pack(a);
+                }
+            }
+        }
+    }
+}
+
+// The partial levels of frame f of channel c, part[f][k][c] for the k tiles
+// the frame has samples in, into level[c][f]: one plain 16-byte store each.
+__global__ __launch_bounds__(kBlock) void fold_kernel(const LevelWords* __restrict__ part, unsigned nch, unsigned F,
+                                                      LevelWords* __restrict__ level) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;   // < nch * F < 2^28
+    if (i >= (size_t)nch * F) return;
+    const size_t f = i / nch, c = i % nch;
+    const unsigned n = (unsigned)(((f + 1) * QK_FRAME - 1) / kTT - f * QK_FRAME / kTT) + 1;   // 15 or 16
+    Acc a;
+    for (unsigned k = 0; k < n; k++) merge(a, unpack(part[(f * QPSK_IN_LEVEL_FRAME_TILES + k) * nch + c]));
+    level[c * F + f] = pack(a);
+}
+
+// Planar G.711 with the level: a wave takes one frame (row) of 1880 codes as
+// level_kernel (qpsk_level.hip) takes one of samples.  A lane takes 8 codes,
+// 235 groups a row in 4 passes, all loads in flight before the first is used,
+// and stores 16 bytes; a wave reads 512 and writes 1024 contiguous bytes a
+// pass.  A row is 1880 = 8 * 235 bytes, so every row has the source's byte
+// offset in an 8-byte word: a group is the two aligned words around it,
+// shifted.  The first group of the block and the last one, whose aligned words
+// would reach outside it, go per element.  Then the wave reduces, and lane 0
+// stores the row's level at once: no partials, no second launch.
+constexpr int kRowVec = QK_FRAME / 8;                       // 235 groups a row
+constexpr int kRowLoads = (kRowVec + kWave - 1) / kWave;   // 4 a lane
+constexpr int kRows = kBlock / kWave;                       // rows of a block at a time
+static_assert(QK_FRAME % 8 == 0 && QPSK_IN_LEVEL_FRAME_TILES * kTT >= QK_FRAME + kTT - 8, "frames and tiles");
+
+template <int ENC, int DEC>
+__global__ __launch_bounds__(kBlock) void planar_level_kernel(const uint8_t* __restrict__ src,
+                                                              int16_t* __restrict__ out, size_t nrows,
+                                                              LevelWords* __restrict__ level) {
+    __shared__ int16_t tab[256];
+    fill_table<ENC, DEC>(tab);
+    __syncthreads();
+    const unsigned lane = threadIdx.x % kWave;
+    const unsigned a = (unsigned)(reinterpret_cast<uintptr_t>(src) & 7u);   // the call's byte offset, every row's
+    const unsigned r = a & 3u;
+    // (whole waves leave the loop: no shuffle below has a lane missing)
+    for (size_t row = (size_t)blockIdx.x * kRows + threadIdx.x / kWave; row < nrows; row += (size_t)gridDim.x * kRows) {
+        const uint8_t* p = src + row * QK_FRAME;
+        const uint2* words = reinterpret_cast<const uint2*>(p - a);
+        unsigned d[kRowLoads][2];
+#pragma unroll
+        for (int k = 0; k < kRowLoads; k++) {
+            const unsigned j = k * kWave + lane;
+            d[k][0] = d[k][1] = 0;
+            if (j >= (unsigned)kRowVec) continue;
+            // word j holds the row's bytes [8j - a, 8j - a + 8), word j + 1 the next 8
+            const bool outside = a != 0 && ((row == 0 && j == 0) || (row == nrows - 1 && j == (unsigned)kRowVec - 1));
+            if (!outside) {
+                const uint2 lo = words[j];
+                const uint2 hi = a ? words[j + 1] : make_uint2(0, 0);
+                if (a < 4) {
+                    d[k][0] = __builtin_amdgcn_alignbyte(lo.y, lo.x, r);
+                    d[k][1] = __builtin_amdgcn_alignbyte(hi.x, lo.y, r);
+                } else {
+                    d[k][0] = __builtin_amdgcn_alignbyte(hi.x, lo.y, r);
+                    d[k][1] = __builtin_amdgcn_alignbyte(hi.y, hi.x, r);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 8; i++) d[k][i / 4] |= (unsigned)p[8 * j + i] << (8 * (i % 4));
+            }
+        }
+        Acc acc;
+#pragma unroll
+        for (int k = 0; k < kRowLoads; k++) {
+            const unsigned j = k * kWave + lane;
+            if (j >= (unsigned)kRowVec) continue;   // (a code of zeros is not a sample of zero)
+            unsigned x[4];
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+                x[2 * q] = decode<ENC, DEC>(d[k][q] & 0xffu, tab) | decode<ENC, DEC>((d[k][q] >> 8) & 0xffu, tab) << 16;
+                x[2 * q + 1] = decode<ENC, DEC>((d[k][q] >> 16) & 0xffu, tab) | decode<ENC, DEC>(d[k][q] >> 24, tab) << 16;
+            }
+            *reinterpret_cast<uint4*>(out + row * QK_FRAME + 8 * (size_t)j) = make_uint4(x[0], x[1], x[2], x[3]);
+            take2(acc, (int)x[0]);
+            take2(acc, (int)x[1]);
+            take2(acc, (int)x[2]);
+            take2(acc, (int)x[3]);
+        }
+        wave_reduce(acc);
+        if (lane == 0) level[row] = pack(acc);
     }
 }
 
@@ -247,6 +407,78 @@ extern "C" int qpsk_input_convert_device_dec(int fmt, const void* d_src, long ld
 extern "C" int qpsk_input_convert_device(int fmt, const void* d_src, long ld, int nch, int nframes,
                                          int16_t* d_out, void* stream) {
     return qpsk_input_convert_device_dec(fmt, d_src, ld, nch, nframes, d_out, stream, QPSK_IN_DEC_DEFAULT);
+}
+
+// ---------------------------------------------------------------- the conversion with the level in its pass
+namespace {
+
+template <int ENC, int DEC>
+void launch_planar_level(const uint8_t* src, int16_t* out, size_t nrows, LevelWords* level, unsigned cap,
+                         hipStream_t s) {
+    hipLaunchKernelGGL((planar_level_kernel<ENC, DEC>), dim3(grid_of((nrows + kRows - 1) / kRows, cap)), dim3(kBlock),
+                       0, s, src, out, nrows, level);
+}
+
+template <int ENC, int W, int DEC>
+void launch_tile_level(const uint8_t* src, size_t ld, unsigned nch, size_t T, int16_t* out, LevelWords* part,
+                       unsigned cap, hipStream_t s) {
+    const unsigned ctiles = (nch + kTC - 1) / kTC;
+    const size_t ntiles = (size_t)ctiles * ((T + kTT - 1) / kTT);
+    hipLaunchKernelGGL((interleaved_kernel<ENC, W, DEC, LevelWords*>), dim3(grid_of(ntiles, cap)), dim3(kBlock), 0, s, src, ld,
+                       nch, T, out, ctiles, ntiles, part);
+}
+
+bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+}  // namespace
+
+extern "C" int qpsk_input_convert_level_device_grid(int fmt, const void* d_src, long ld, int nch, int nframes,
+                                                    int16_t* d_out, qpsk_frame_level* d_level, void* d_work,
+                                                    size_t work_bytes, void* stream, int dec, unsigned grid_cap) {
+    if (qpsk_input_check(fmt, nch, nframes, ld) != QPSK_OK) return QPSK_EINVAL;
+    const bool planar = QPSK_FMT_LAYOUT(fmt) == QPSK_IN_PLANAR;
+    if (dec == QPSK_IN_DEC_DEFAULT) dec = planar ? QPSK_IN_DEC_TABLE : QPSK_IN_DEC_ARITH;
+    if (dec != QPSK_IN_DEC_ARITH && dec != QPSK_IN_DEC_TABLE) return QPSK_EINVAL;
+    if (nframes == 0) return QPSK_OK;
+    const int es = qpsk_fmt_esize(fmt), enc = QPSK_FMT_ENC(fmt);
+    if (!d_src || !d_out || !aligned_to(d_out, 16) || !aligned_to(d_src, (uintptr_t)es)) return QPSK_EINVAL;
+    const size_t need = qpsk_input_level_work(fmt, nch, nframes, ld);
+    if (!d_level || !aligned_to(d_level, 8) || !aligned_to(d_work, 16) || work_bytes < need || (need > 0 && !d_work))
+        return QPSK_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const uint8_t* src = static_cast<const uint8_t*>(d_src);
+    const size_t T = (size_t)nframes * QK_FRAME, nrows = (size_t)nch * (size_t)nframes;
+    const bool table = dec == QPSK_IN_DEC_TABLE;
+    const unsigned cap = grid_cap ? grid_cap : kMaxGrid;
+    LevelWords* level = reinterpret_cast<LevelWords*>(d_level);
+    if (planar) {
+        if (enc == QPSK_IN_S16) {   // no conversion pass: the copy, then the meter's own kernel on what it wrote
+            HCHECK(hipMemcpyAsync(d_out, d_src, nrows * QK_FRAME * sizeof(int16_t), hipMemcpyDeviceToDevice, s));
+            return qpsk_level_device(d_out, nrows, d_level, s);
+        }
+        with_decoder(enc, table, [&](auto e, auto d) {
+            if constexpr (e() != QPSK_IN_S16) launch_planar_level<e(), d()>(src, d_out, nrows, level, cap, s);
+        });
+    } else {
+        LevelWords* part = static_cast<LevelWords*>(d_work);
+        const int w = qpsk_input_load_width(d_src, ld, es);
+        with_decoder(enc, table, [&](auto e, auto d) {
+            with_width<esize_of(e())>(w, [&](auto wc) {
+                launch_tile_level<e(), wc(), d()>(src, (size_t)ld, (unsigned)nch, T, d_out, part, cap, s);
+            });
+        });
+        hipLaunchKernelGGL(fold_kernel, dim3((unsigned)((nrows + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, part,
+                           (unsigned)nch, (unsigned)nframes, level);
+    }
+    HCHECK(hipGetLastError());
+    return QPSK_OK;
+}
+
+extern "C" int qpsk_input_convert_level_device(int fmt, const void* d_src, long ld, int nch, int nframes,
+                                               int16_t* d_out, qpsk_frame_level* d_level, void* d_work,
+                                               size_t work_bytes, void* stream) {
+    return qpsk_input_convert_level_device_grid(fmt, d_src, ld, nch, nframes, d_out, d_level, d_work, work_bytes,
+                                                stream, QPSK_IN_DEC_DEFAULT, 0);
 }
 
 // ---------------------------------------------------------------- the receive path behind it

@@ -24,7 +24,10 @@
 //
 // The record entry points are built on the hooks of qpsk_rx_internal.h as
 // qpsk_compact.hip builds its own: the receive, stream and compaction units
-// refer to nothing of this file.
+// refer to nothing of this file.  For input in another format than planar
+// int16 (the _fmt calls, squelch streams) the levels come from the conversion's
+// own pass (qpsk_input_convert_level_device, qpsk_input.hip), not from
+// level_kernel.  What level_kernel shares with that pass is qpsk_level_dev.h.
 // Not part of the receive kernels' hash (csrc/Makefile KSRC).
 #include <hip/hip_runtime.h>
 
@@ -35,15 +38,19 @@
 #include "qpsk_compact.h"
 #include "qpsk_compact_tile.h"
 #include "qpsk_consts.h"
+#include "qpsk_fmt.h"
 #include "qpsk_herr.h"
+#include "qpsk_input.h"
 #include "qpsk_level.h"
+#include "qpsk_level_dev.h"
 #include "qpsk_level_tile.h"
 #include "qpsk_rx_internal.h"
 #include "qpsk_rx_plan.h"
 
 namespace {
 
-constexpr int kWave = 64;
+using namespace qlevel;   // kWave, LevelWords, Acc, take2
+
 constexpr int kRows = QPSK_LEVEL_BLOCK_ROWS;
 constexpr int kBlock = kRows * kWave;
 constexpr int kVec = 8;                                   // samples of a 16-byte word
@@ -53,31 +60,7 @@ constexpr int kSqBlock = 256;
 constexpr unsigned kSoftQw = QK_NDSYM;                    // a soft row in 8-byte words
 constexpr uintptr_t kAlignLevel = 8;
 static_assert(QK_FRAME % kVec == 0 && kBlock <= 1024, "meter tiling");
-static_assert(sizeof(qpsk_frame_level) == 16, "level layout");
 static_assert(QK_NBITS % 2 == 0 && sizeof(float) * 2 * QK_NDSYM == 8 * kSoftQw, "row alignments");
-
-// a level as it is stored: two 8-byte words at the array's 8-byte alignment
-struct alignas(8) LevelWords {
-    unsigned long long sumsq, rest;   // rest: sum | peak << 32 | clipped << 48
-};
-static_assert(sizeof(LevelWords) == sizeof(qpsk_frame_level), "level layout");
-
-struct Acc {
-    unsigned long long sumsq = 0;
-    int sum = 0;
-    unsigned peak = 0, clipped = 0;
-};
-
-// the two samples of a word
-__device__ __forceinline__ void take2(Acc& a, int w) {
-    const int lo = (int)(short)(w & 0xffff), hi = w >> 16;
-    const unsigned alo = (unsigned)(lo < 0 ? -lo : lo), ahi = (unsigned)(hi < 0 ? -hi : hi);
-    a.sumsq += alo * alo + ahi * ahi;   // <= 2^31: an unsigned word holds the pair
-    a.sum += lo + hi;
-    a.peak = max(a.peak, max(alo, ahi));
-    // v ^ (v >> 31) is v for v >= 0 and -v - 1 below: 32767 at either rail
-    a.clipped += (unsigned)((lo ^ (lo >> 31)) == 32767) + (unsigned)((hi ^ (hi >> 31)) == 32767);
-}
 
 __global__ __launch_bounds__(kBlock) void level_kernel(const int4* __restrict__ in, size_t nrows,
                                                        LevelWords* __restrict__ out) {
@@ -99,6 +82,7 @@ __global__ __launch_bounds__(kBlock) void level_kernel(const int4* __restrict__ 
         take2(a, v[k].z);
         take2(a, v[k].w);
     }
+    // (wave_reduce and pack of qpsk_level_dev.h, written out: see there)
 #pragma unroll
     for (int d = kWave / 2; d > 0; d >>= 1) {
         a.sumsq += __shfl_xor(a.sumsq, d, kWave);
@@ -240,22 +224,40 @@ struct Made {
     qpsk_frame_level* level;
 };
 
-// Receive, meter, squelch and compaction of d_in on s.  A device call gives
-// its own pointers; a host call (out != nullptr) gets the results in the
-// context's block, with prev_host copied in behind the buffers' growth.
-// want_trace / want_soft: whether those rows are made.
-int enqueue(const Call& k, const int16_t* d_in, qpsk_frame_level* d_prev_io, qpsk_frame_rec* d_rec,
+// The input of a call on the device: a block in format fmt (include/qpsk_input.h)
+struct In {
+    const void* d;
+    int fmt;
+    long ld;
+    bool planar16() const { return fmt == (QPSK_IN_S16 | QPSK_IN_PLANAR); }
+};
+
+// Receive, meter, squelch and compaction of `in` on s.  Planar int16 is
+// received where it lies and metered by level_kernel; a block in any other
+// format is converted into the context's buffer by the pass that also takes
+// the levels (qpsk_input_convert_level_device): no level_kernel launch.  A
+// device call gives its own pointers; a host call (out != nullptr) gets the
+// results in the context's block, with prev_host copied in behind the buffers'
+// growth.  want_trace / want_soft: whether those rows are made.
+int enqueue(const Call& k, const In& in, qpsk_frame_level* d_prev_io, qpsk_frame_rec* d_rec,
             int32_t* d_rec_trace, float* d_rec_soft, uint32_t* d_groups, uint32_t* d_count, qpsk_frame_level* d_level,
             bool want_trace, bool want_soft, const OutBlock* out, const qpsk_frame_level* prev_host, Made* made,
             hipStream_t s) {
     const int nch = qpsk_rx_channels(k.c), F = k.F;
     const size_t cf = (size_t)nch * (size_t)F;
-    // the receive's own refusal of a misaligned input (qpsk_rx_plan.h), in front of the context's buffers
-    if (F > 0 && !rx_ptrs_aligned(d_in, nullptr, nullptr, nullptr, nullptr)) return QPSK_EINVAL;
+    const bool p16 = in.planar16();
+    // the receive's own refusal of a misaligned input (qpsk_rx_plan.h), or the
+    // conversion's, in front of the context's buffers
+    if (F > 0 && (p16 ? !rx_ptrs_aligned(static_cast<const int16_t*>(in.d), nullptr, nullptr, nullptr, nullptr)
+                      : !aligned(in.d, (uintptr_t)qpsk_fmt_esize(in.fmt))))
+        return QPSK_EINVAL;
     if (!aligned(d_prev_io, kAlignLevel) || !aligned(d_level, kAlignLevel)) return QPSK_EINVAL;
-    // the work area: the compaction's counts, then the levels where the caller takes none
+    // the work area: the compaction's counts, then the levels where the caller
+    // takes none, then the partial levels of the conversion's pass
     const size_t cwork = qpsk_compact_work_bytes(nch, F), lvl_at = up16(cwork);
-    const size_t work = lvl_at + (d_level ? 0 : cf * sizeof(qpsk_frame_level));
+    const size_t part_at = up16(lvl_at + (d_level ? 0 : cf * sizeof(qpsk_frame_level)));
+    const size_t part_bytes = p16 ? 0 : qpsk_input_level_work(in.fmt, nch, F, in.ld);
+    const size_t work = part_at + part_bytes;
     qpsk_rec_bufs& b = made->b;
     int r = qpsk_rx_rec_bufs(k.c, cf, want_trace, want_soft, work, out ? out->end : 0, &b);
     if (r != QPSK_OK) return r;
@@ -273,11 +275,23 @@ int enqueue(const Call& k, const int16_t* d_in, qpsk_frame_level* d_prev_io, qps
     }
     if (!d_level) d_level = reinterpret_cast<qpsk_frame_level*>(static_cast<char*>(b.work) + lvl_at);
     made->level = d_level;
+    const int16_t* d_in = static_cast<const int16_t*>(in.d);
+    if (!p16 && F > 0) {   // the receive's input and the levels in one pass over the source
+        int16_t* conv = nullptr;
+        r = qpsk_rx_fmt_conv(k.c, cf * QK_FRAME, &conv);
+        if (r != QPSK_OK) return r;
+        r = qpsk_input_convert_level_device(in.fmt, in.d, in.ld, nch, F, conv, d_level,
+                                            static_cast<char*>(b.work) + part_at, part_bytes, s);
+        if (r != QPSK_OK) return r;
+        d_in = conv;
+    }
     r = qpsk_rx_batch_device(k.c, d_in, F, b.bits, b.valid, b.trace, b.soft, s);
     if (r != QPSK_OK) return r;
     if (F > 0) {
-        r = qpsk_level_device(d_in, cf, d_level, s);
-        if (r != QPSK_OK) return r;
+        if (p16) {
+            r = qpsk_level_device(d_in, cf, d_level, s);
+            if (r != QPSK_OK) return r;
+        }
         // the flags in place; the rows of squelched frames stay as they are:
         // the compaction reads the rows of valid frames only
         r = qpsk_squelch_device(d_level, d_prev_io, nch, F, k.min_sumsq, b.valid, b.valid, nullptr, nullptr, d_prev_io, s);
@@ -293,29 +307,43 @@ int enqueue(const Call& k, const int16_t* d_in, qpsk_frame_level* d_prev_io, qps
 
 }  // namespace
 
+extern "C" int qpsk_rx_batch_records_squelch_device_fmt(qpsk_ctx* c, const void* d_in, int fmt, long ld, int F,
+                                                        uint64_t min_sumsq, qpsk_frame_level* d_prev_io, int order,
+                                                        size_t cap, qpsk_frame_rec* d_rec, int32_t* d_rec_trace,
+                                                        float* d_rec_soft, uint32_t* d_groups, uint32_t* d_count,
+                                                        qpsk_frame_level* d_level, void* stream) {
+    const Call k{c, F, min_sumsq, order, cap};
+    const int r = call_check(k, d_rec, d_count);
+    if (r != QPSK_OK) return r;
+    const In in{d_in, fmt, ld};
+    if (!in.planar16() && qpsk_input_check(fmt, qpsk_rx_channels(c), F, ld) != QPSK_OK) return QPSK_EINVAL;
+    if (F > 0 && !d_in) return QPSK_EINVAL;
+    Made made{};
+    return enqueue(k, in, d_prev_io, d_rec, d_rec_trace, d_rec_soft, d_groups, d_count, d_level,
+                   d_rec_trace != nullptr, d_rec_soft != nullptr, nullptr, nullptr, &made, (hipStream_t)stream);
+}
+
 extern "C" int qpsk_rx_batch_records_squelch_device(qpsk_ctx* c, const int16_t* d_in, int F, uint64_t min_sumsq,
                                                     qpsk_frame_level* d_prev_io, int order, size_t cap,
                                                     qpsk_frame_rec* d_rec, int32_t* d_rec_trace, float* d_rec_soft,
                                                     uint32_t* d_groups, uint32_t* d_count, qpsk_frame_level* d_level,
                                                     void* stream) {
-    const Call k{c, F, min_sumsq, order, cap};
-    const int r = call_check(k, d_rec, d_count);
-    if (r != QPSK_OK) return r;
-    if (F > 0 && !d_in) return QPSK_EINVAL;
-    Made made{};
-    return enqueue(k, d_in, d_prev_io, d_rec, d_rec_trace, d_rec_soft, d_groups, d_count, d_level,
-                   d_rec_trace != nullptr, d_rec_soft != nullptr, nullptr, nullptr, &made, (hipStream_t)stream);
+    return qpsk_rx_batch_records_squelch_device_fmt(c, d_in, QPSK_IN_S16 | QPSK_IN_PLANAR, 0, F, min_sumsq, d_prev_io,
+                                                    order, cap, d_rec, d_rec_trace, d_rec_soft, d_groups, d_count,
+                                                    d_level, stream);
 }
 
-extern "C" int qpsk_rx_batch_records_squelch(qpsk_ctx* c, const int16_t* in, int F, uint64_t min_sumsq,
-                                             qpsk_frame_level* prev_io, int order, size_t cap, qpsk_frame_rec* rec,
-                                             int32_t* rec_trace, float* rec_soft, uint32_t* groups, uint32_t* count,
-                                             qpsk_frame_level* level) {
+extern "C" int qpsk_rx_batch_records_squelch_fmt(qpsk_ctx* c, const void* in, int fmt, long ld, int F,
+                                                 uint64_t min_sumsq, qpsk_frame_level* prev_io, int order, size_t cap,
+                                                 qpsk_frame_rec* rec, int32_t* rec_trace, float* rec_soft,
+                                                 uint32_t* groups, uint32_t* count, qpsk_frame_level* level) {
     Call k{c, F, min_sumsq, order, cap};
     int r = call_check(k, rec, count);
     if (r != QPSK_OK) return r;
-    if (F > 0 && !in) return QPSK_EINVAL;
     const int nch = qpsk_rx_channels(c);
+    const bool p16 = fmt == (QPSK_IN_S16 | QPSK_IN_PLANAR);
+    if (!p16 && qpsk_input_check(fmt, nch, F, ld) != QPSK_OK) return QPSK_EINVAL;
+    if (F > 0 && !in) return QPSK_EINVAL;
     const size_t cf = (size_t)nch * (size_t)F;
     const size_t G = (size_t)(order == QPSK_REC_BY_FRAME ? F : nch);
     const size_t m = cap < cf ? cap : cf;   // rows there can be
@@ -324,11 +352,20 @@ extern "C" int qpsk_rx_batch_records_squelch(qpsk_ctx* c, const int16_t* in, int
     // a device call still pending on a caller's stream uses the buffers taken below
     r = qpsk_rx_wait_pending(c);
     if (r != QPSK_OK) return r;
-    int16_t* d_in = nullptr;
-    if (F > 0) {
-        r = qpsk_rx_fmt_conv(c, cf * QK_FRAME, &d_in);
+    In d_in{nullptr, fmt, ld};
+    if (F > 0 && p16) {
+        int16_t* conv = nullptr;
+        r = qpsk_rx_fmt_conv(c, cf * QK_FRAME, &conv);
         if (r != QPSK_OK) return r;
-        HCHECK(hipMemcpyAsync(d_in, in, sizeof(int16_t) * cf * QK_FRAME, hipMemcpyHostToDevice, s));
+        HCHECK(hipMemcpyAsync(conv, in, sizeof(int16_t) * cf * QK_FRAME, hipMemcpyHostToDevice, s));
+        d_in.d = conv;
+    } else if (F > 0) {   // the source block over PCIe as it is
+        const size_t nraw = qpsk_input_bytes(fmt, nch, F, ld);
+        char* raw = nullptr;
+        r = qpsk_rx_fmt_raw(c, nraw, &raw);
+        if (r != QPSK_OK) return r;
+        HCHECK(hipMemcpyAsync(raw, in, nraw, hipMemcpyHostToDevice, s));
+        d_in.d = raw;
     }
     const OutBlock o(G, m, rec_trace != nullptr, rec_soft != nullptr, prev_io ? (size_t)nch : 0);
     Made made{};
@@ -357,4 +394,78 @@ extern "C" int qpsk_rx_batch_records_squelch(qpsk_ctx* c, const int16_t* in, int
         HCHECK(hipStreamSynchronize(s));
     }
     return verdict;
+}
+
+extern "C" int qpsk_rx_batch_records_squelch(qpsk_ctx* c, const int16_t* in, int F, uint64_t min_sumsq,
+                                             qpsk_frame_level* prev_io, int order, size_t cap, qpsk_frame_rec* rec,
+                                             int32_t* rec_trace, float* rec_soft, uint32_t* groups, uint32_t* count,
+                                             qpsk_frame_level* level) {
+    return qpsk_rx_batch_records_squelch_fmt(c, in, QPSK_IN_S16 | QPSK_IN_PLANAR, 0, F, min_sumsq, prev_io, order, cap,
+                                             rec, rec_trace, rec_soft, groups, count, level);
+}
+
+// ---------------------------------------------------------------- streams of records with squelch
+namespace {
+
+int stream_convert_level(int fmt, const void* d_src, long ld, int nch, int nframes, int16_t* d_out, void* d_level,
+                         void* d_work, size_t work_bytes, void* stream) {
+    return qpsk_input_convert_level_device(fmt, d_src, ld, nch, nframes, d_out, static_cast<qpsk_frame_level*>(d_level),
+                                           d_work, work_bytes, stream);
+}
+
+// the chunk's levels (made here from planar int16 input), the gate with the
+// stream's carried levels as prev and last, then the compaction
+int stream_squelch_compact(const int16_t* d_in, bool have_level, void* d_level, void* d_carry, uint64_t min_sumsq,
+                           const uint8_t* d_bits, uint8_t* d_valid, int nch, int nframes, int order, size_t cap,
+                           void* d_rec, uint32_t* d_groups, uint32_t* d_count, void* d_work, size_t work_bytes,
+                           void* stream) {
+    qpsk_frame_level* level = static_cast<qpsk_frame_level*>(d_level);
+    qpsk_frame_level* carry = static_cast<qpsk_frame_level*>(d_carry);
+    int r = have_level ? QPSK_OK : qpsk_level_device(d_in, (size_t)nch * (size_t)nframes, level, stream);
+    if (r != QPSK_OK) return r;
+    r = qpsk_squelch_device(level, carry, nch, nframes, min_sumsq, d_valid, d_valid, nullptr, nullptr, carry, stream);
+    if (r != QPSK_OK) return r;
+    return qpsk_compact_device(d_bits, d_valid, nullptr, nullptr, nch, nframes, order, cap,
+                               static_cast<qpsk_frame_rec*>(d_rec), nullptr, nullptr, d_groups, d_count, d_work,
+                               work_bytes, stream);
+}
+
+}  // namespace
+
+extern "C" qpsk_stream* qpsk_stream_create_records_squelch(int device, int nch, int frames, int nslot, int mode, int fmt,
+                                                           int order, size_t cap, uint64_t min_sumsq, int* err) {
+    const bool planar16 = fmt == (QPSK_IN_S16 | QPSK_IN_PLANAR);
+    if ((order != QPSK_REC_BY_CHANNEL && order != QPSK_REC_BY_FRAME) || nch < 1 || frames < 1 ||
+        (uint64_t)nch * (uint64_t)frames >= QPSK_COMPACT_MAX_ITEMS ||
+        (!planar16 && qpsk_input_check(fmt, nch, frames, nch) != QPSK_OK)) {
+        if (err) *err = QPSK_EINVAL;
+        return nullptr;
+    }
+    const size_t cf = (size_t)nch * (size_t)frames;
+    qpsk_stream_post p;
+    p.order = order;
+    p.cap = cap < cf ? cap : cf;   // a chunk has no more
+    p.rec_bytes = sizeof(qpsk_frame_rec);
+    p.ngroups = (size_t)(order == QPSK_REC_BY_FRAME ? frames : nch);
+    p.work_bytes = qpsk_compact_work_bytes(nch, frames);
+    p.level_bytes = sizeof(qpsk_frame_level);
+    p.level_work_bytes = planar16 ? 0 : qpsk_input_level_work(fmt, nch, frames, nch);
+    p.arg = min_sumsq;
+    p.convert_level = planar16 ? nullptr : stream_convert_level;
+    p.compact_level = stream_squelch_compact;
+    return qpsk_stream_create_post(device, nch, frames, nslot, mode, fmt,
+                                   planar16 ? 0 : qpsk_input_bytes(fmt, nch, frames, nch),
+                                   planar16 ? nullptr : qpsk_input_convert_device, &p, err);
+}
+
+extern "C" int qpsk_stream_retrieve_records_squelch(qpsk_stream* s, const qpsk_frame_rec** rec, uint32_t* count,
+                                                    const uint32_t** groups, const qpsk_frame_level** level) {
+    if (!rec) return QPSK_EINVAL;
+    const void *r = nullptr, *l = nullptr;
+    const int v = qpsk_stream_retrieve_post_level(s, &r, count, groups, level ? &l : nullptr);
+    if (v != QPSK_EINVAL) {
+        *rec = static_cast<const qpsk_frame_rec*>(r);
+        if (level) *level = static_cast<const qpsk_frame_level*>(l);
+    }
+    return v;
 }

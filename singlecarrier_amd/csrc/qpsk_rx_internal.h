@@ -95,6 +95,23 @@ struct qpsk_stream_post {
     int (*compact)(const uint8_t* d_bits, const uint8_t* d_valid, int nch, int nframes, int order, size_t cap,
                    void* d_rec, uint32_t* d_groups, uint32_t* d_count, void* d_work, size_t work_bytes,
                    void* stream) = nullptr;
+    // A pass that also takes the level of every input frame (level_bytes > 0:
+    // the bytes of one level).  The slot keeps the chunk's levels [nch][frames]
+    // on the device, the stream a carried array [nch] of them, zero at
+    // creation, which every chunk's pass reads and writes in submit order.
+    // convert_level (nullptr for planar int16 chunks) runs in place of the
+    // stream's convert and writes the levels too, with a work area of
+    // level_work_bytes; compact_level runs in place of compact, with the
+    // slot's input (have_level == false: the levels are still to be made from
+    // it), the levels, the carried array and `arg`, and may change d_valid.
+    size_t level_bytes = 0, level_work_bytes = 0;
+    uint64_t arg = 0;
+    int (*convert_level)(int fmt, const void* d_src, long ld, int nch, int nframes, int16_t* d_out, void* d_level,
+                         void* d_work, size_t work_bytes, void* stream) = nullptr;
+    int (*compact_level)(const int16_t* d_in, bool have_level, void* d_level, void* d_carry, uint64_t arg,
+                         const uint8_t* d_bits, uint8_t* d_valid, int nch, int nframes, int order, size_t cap,
+                         void* d_rec, uint32_t* d_groups, uint32_t* d_count, void* d_work, size_t work_bytes,
+                         void* stream) = nullptr;
 };
 struct qpsk_stream;
 // qpsk_stream_create_raw (convert may be nullptr: planar int16 chunks) with a
@@ -104,6 +121,11 @@ qpsk_stream* qpsk_stream_create_post(int device, int nch, int frames, int nslot,
                                      int* err);
 // qpsk_stream_retrieve for such a stream (QPSK_EINVAL on any other)
 int qpsk_stream_retrieve_post(qpsk_stream* s, const void** rec, uint32_t* count, const uint32_t** groups);
+// The same, and the chunk's levels (level != nullptr; QPSK_EINVAL on a stream
+// whose pass takes none): copied to the slot's pinned memory on retrieval, as
+// the records are, and good until the slot is acquired again.
+int qpsk_stream_retrieve_post_level(qpsk_stream* s, const void** rec, uint32_t* count, const uint32_t** groups,
+                                    const void** level);
 
 // The stream that owns a context (qpsk_stream_create_mode): qpsk_rx_reset()
 // and qpsk_rx_state_load() refuse with QPSK_EBUSY while it has chunks pending.

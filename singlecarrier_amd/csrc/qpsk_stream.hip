@@ -36,6 +36,10 @@ struct Slot {
     qhip::PinBuf<char> h_rec;
     qhip::DevBuf<uint32_t> d_hdr;
     qhip::PinBuf<uint32_t> h_hdr;
+    // a post stream whose pass takes the input's levels: the chunk's, on the
+    // device and (copied on retrieval, when asked for) pinned
+    qhip::DevBuf<char> d_level;
+    qhip::PinBuf<char> h_level;
     qhip::Event copied, received, done;
     uint64_t epoch = 0;          // qpsk_rx_epoch() when the chunk was submitted
 };
@@ -59,6 +63,10 @@ struct qpsk_stream {
     bool has_post = false;
     qpsk_stream_post post;
     qhip::DevBuf<char> work;   // the pass's work area: one, the passes run in order on s_rx
+    // a pass with levels: the conversion's work area, and the levels carried
+    // from chunk to chunk [nch], zero at creation
+    bool has_level() const { return has_post && post.level_bytes != 0; }
+    qhip::DevBuf<char> level_work, carry;
     // released in reverse order: the slots, the streams, then the receiver
     struct RxDestroy {
         void operator()(qpsk_ctx* c) const { qpsk_rx_destroy(c); }
@@ -86,6 +94,12 @@ static int stream_alloc(qpsk_stream* s) {
         HCHECK(s->s_rec.create());
         HCHECK(s->work.reserve(s->post.work_bytes));
     }
+    if (s->has_level()) {
+        HCHECK(s->level_work.reserve(s->post.level_work_bytes));
+        HCHECK(s->carry.reserve((size_t)s->nch * s->post.level_bytes));
+        // the start of a stream; on s_rx, in front of every pass that reads it
+        HCHECK(hipMemsetAsync(s->carry, 0, (size_t)s->nch * s->post.level_bytes, s->s_rx));
+    }
     const size_t cf = (size_t)s->nch * (size_t)s->frames;
     for (int i = 0; i < s->nslot; i++) {
         Slot& q = s->slot[i];
@@ -100,6 +114,10 @@ static int stream_alloc(qpsk_stream* s) {
             HCHECK(q.d_rec.reserve(s->post.cap * s->post.rec_bytes));
             HCHECK(q.d_hdr.reserve(s->post.ngroups + 2));
             HCHECK(q.h_hdr.reserve(s->post.ngroups + 2));
+            if (s->has_level()) {
+                HCHECK(q.d_level.reserve(cf * s->post.level_bytes));
+                HCHECK(q.h_level.reserve(cf * s->post.level_bytes));
+            }
         } else {
             HCHECK(q.h_bits.reserve(cf * QK_NBITS));
             HCHECK(q.h_valid.reserve(cf));
@@ -135,7 +153,11 @@ qpsk_stream* qpsk_stream_create_post(int device, int nch, int frames, int nslot,
                                      int* err) {
     if (nch < 1 || frames < 1 || nslot < 1 || nslot > kMaxSlots) return qhip::fail(err, QPSK_EINVAL);
     if (convert && raw_bytes == 0) return qhip::fail(err, QPSK_EINVAL);
-    if (post && (!post->compact || post->rec_bytes == 0)) return qhip::fail(err, QPSK_EINVAL);
+    if (post && ((post->level_bytes ? !post->compact_level : !post->compact) || post->rec_bytes == 0))
+        return qhip::fail(err, QPSK_EINVAL);
+    // (a pass with levels converts with its own hook wherever the stream converts)
+    if (post && post->level_bytes && (convert != nullptr) != (post->convert_level != nullptr))
+        return qhip::fail(err, QPSK_EINVAL);
     qpsk_stream* s = new (std::nothrow) qpsk_stream();
     if (!s) return qhip::fail(err, QPSK_ENOMEM);
     s->device = device;
@@ -212,7 +234,10 @@ extern "C" int qpsk_stream_submit(qpsk_stream* s) {
     HCHECK(hipEventRecord(q.copied, s->s_h2d));
     HCHECK(hipStreamWaitEvent(s->s_rx, q.copied, 0));
     if (!s->plain()) {   // the narrow block -> int16 [nch][frames][1880], in front of the receive
-        const int cr = s->convert(s->fmt, q.d_raw, s->nch, s->nch, s->frames, q.d_in, s->s_rx);
+        const int cr = s->has_level()
+                           ? s->post.convert_level(s->fmt, q.d_raw, s->nch, s->nch, s->frames, q.d_in, q.d_level,
+                                                   s->level_work, s->post.level_work_bytes, s->s_rx)
+                           : s->convert(s->fmt, q.d_raw, s->nch, s->nch, s->frames, q.d_in, s->s_rx);
         if (cr != QPSK_OK) return cr;
     }
     HCHECK(hipMemsetAsync(q.d_err, 0, sizeof(int), s->s_rx));
@@ -223,8 +248,12 @@ extern "C" int qpsk_stream_submit(qpsk_stream* s) {
     HCHECK(hipGetLastError());
     if (s->has_post) {   // the dense outputs -> records, count and groups, behind the receive
         const qpsk_stream_post& p = s->post;
-        const int pr = p.compact(q.d_bits, q.d_valid, s->nch, s->frames, p.order, p.cap,
-                                 q.d_rec, q.d_hdr + 1, q.d_hdr, s->work, p.work_bytes, s->s_rx);
+        const int pr = s->has_level()
+                           ? p.compact_level(q.d_in, !s->plain(), q.d_level, s->carry, p.arg, q.d_bits, q.d_valid,
+                                             s->nch, s->frames, p.order, p.cap, q.d_rec, q.d_hdr + 1, q.d_hdr,
+                                             s->work, p.work_bytes, s->s_rx)
+                           : p.compact(q.d_bits, q.d_valid, s->nch, s->frames, p.order, p.cap, q.d_rec, q.d_hdr + 1,
+                                       q.d_hdr, s->work, p.work_bytes, s->s_rx);
         if (pr != QPSK_OK) return pr;
     }
     HCHECK(hipEventRecord(q.received, s->s_rx));
@@ -274,7 +303,13 @@ extern "C" int qpsk_stream_retrieve(qpsk_stream* s, const uint8_t** bits, const 
 }
 
 int qpsk_stream_retrieve_post(qpsk_stream* s, const void** rec, uint32_t* count, const uint32_t** groups) {
+    return qpsk_stream_retrieve_post_level(s, rec, count, groups, nullptr);
+}
+
+int qpsk_stream_retrieve_post_level(qpsk_stream* s, const void** rec, uint32_t* count, const uint32_t** groups,
+                                    const void** level) {
     if (!s || !s->has_post || !rec || !count || !groups || s->retrieved == s->submitted) return QPSK_EINVAL;
+    if (level && !s->has_level()) return QPSK_EINVAL;
     Slot& q = s->slot[s->retrieved % (uint64_t)s->nslot];
     HCHECK(hipSetDevice(s->device));
     HCHECK(hipEventSynchronize(q.done));
@@ -283,10 +318,13 @@ int qpsk_stream_retrieve_post(qpsk_stream* s, const void** rec, uint32_t* count,
     *rec = q.h_rec;
     // the count is known: that many records, at most cap, and nothing else
     const size_t m = *count < s->post.cap ? (size_t)*count : s->post.cap;
-    if (m > 0) {
-        HCHECK(hipMemcpyAsync(q.h_rec, q.d_rec, m * s->post.rec_bytes, hipMemcpyDeviceToHost, s->s_rec));
-        HCHECK(hipStreamSynchronize(s->s_rec));
+    if (m > 0) HCHECK(hipMemcpyAsync(q.h_rec, q.d_rec, m * s->post.rec_bytes, hipMemcpyDeviceToHost, s->s_rec));
+    if (level) {
+        HCHECK(hipMemcpyAsync(q.h_level, q.d_level, (size_t)s->nch * (size_t)s->frames * s->post.level_bytes,
+                              hipMemcpyDeviceToHost, s->s_rec));
+        *level = q.h_level;
     }
+    if (m > 0 || level) HCHECK(hipStreamSynchronize(s->s_rec));
     return retrieved_verdict(s, q);
 }
 
