@@ -12,12 +12,15 @@
  *                                            the batch as one timeslot-interleaved trunk file:
  *                                            one sample of every channel after another, what
  *                                            qpsk_rx_stream -i NCH reads
+ *   -a    with -b: send every file to its own end.  A channel whose file has ended goes idle
+ *         (zeros on its line, qpsk_tx_batch_masked_fmt) while the others keep sending, instead
+ *         of all stopping at the shortest file
  *   -f s16|alaw|ulaw   int16 samples (default) or 8-bit G.711 codes, made on the GPU
  *   -c    modulate on the host (qpsk_tx_batch_host, qpsk_output_convert_host) instead of the GPU
  *
  * Input: 0/1 bytes, 496 per packet (8 frames of 62 bits, bits[2s] = Q,
  * bits[2s+1] = I: the layout qpsk_rx_raw writes); a short tail is dropped, and
- * -b sends the packets every file has.  Output: the reference's .raw framing,
+ * -b sends the packets every file has (-a: the packets any file has).  Output: the reference's .raw framing,
  * samples at 8 kHz: per packet 640 preamble samples, 8 x 155 data samples, GAP
  * zeros (default 903, as the reference writes).
  */
@@ -54,43 +57,48 @@ static int fail(int err) {
 
 /* names[c] is channel c's output file; with QPSK_OUT_INTERLEAVED in fmt,
  * names[0] is the trunk's */
-static int run(int nch, char **paths, char **names, int gap, int host, int fmt) {
+static int run(int nch, char **paths, char **names, int gap, int host, int fmt, int all) {
     int npk = -1;
     uint8_t **ch = calloc((size_t)nch, sizeof(uint8_t *));
-    if (!ch) return 1;
+    int *have = calloc((size_t)nch, sizeof(int));
+    if (!ch || !have) return 1;
     for (int c = 0; c < nch; c++) {
-        int n;
-        ch[c] = read_packets(paths[c], &n);
+        ch[c] = read_packets(paths[c], &have[c]);
         if (!ch[c]) {
             fprintf(stderr, "cannot read %s\n", paths[c]);
             return 1;
         }
-        if (npk < 0 || n < npk) npk = n;
+        if (npk < 0 || (all ? have[c] > npk : have[c] < npk)) npk = have[c];
     }
     if (npk <= 0) return 1;
     const long n = (long)npk * (TX_PACKET + (long)gap);
     const int trunk = (fmt & QPSK_OUT_INTERLEAVED) != 0;
     const long ld = trunk ? nch : n;
     const size_t es = (fmt & 0x0f) == QPSK_OUT_S16 ? sizeof(int16_t) : 1;
-    uint8_t *bits = malloc((size_t)nch * npk * PACKET_BITS);
+    uint8_t *bits = calloc((size_t)nch * npk, PACKET_BITS);
     uint8_t *out = malloc(es * (size_t)nch * (size_t)n);
-    if (!bits || !out) return 1;
-    for (int c = 0; c < nch; c++)
-        memcpy(bits + (size_t)c * npk * PACKET_BITS, ch[c], (size_t)npk * PACKET_BITS);
+    /* -a: slot k of channel c is active while its file lasts; the rows of idle slots are not read */
+    uint8_t *active = all ? calloc((size_t)nch, (size_t)npk) : NULL;
+    if (!bits || !out || (all && !active)) return 1;
+    for (int c = 0; c < nch; c++) {
+        const int mine = have[c] < npk ? have[c] : npk;
+        memcpy(bits + (size_t)c * npk * PACKET_BITS, ch[c], (size_t)mine * PACKET_BITS);
+        if (all) memset(active + (size_t)c * npk, 1, (size_t)mine);
+    }
     int err = QPSK_OK;
     if (host) {
         qpsk_tx_state *st = malloc(sizeof(qpsk_tx_state) * (size_t)nch);
         int16_t *lin = malloc(sizeof(int16_t) * (size_t)nch * (size_t)n);
         if (!st || !lin) return 1;
         for (int c = 0; c < nch; c++) qpsk_tx_state_init(&st[c]);
-        err = qpsk_tx_batch_host(st, nch, bits, npk, gap, lin, n, 4);
+        err = qpsk_tx_batch_masked_host(st, nch, bits, active, npk, gap, lin, n, 4);
         if (!err) err = qpsk_output_convert_host(fmt, lin, n, nch, n, out, ld, 4);
         free(lin);
         free(st);
     } else {
         qpsk_tx_ctx *ctx = qpsk_tx_create(0, nch, gap, &err);
         if (!ctx) return fail(err);
-        err = qpsk_tx_batch_fmt(ctx, bits, npk, out, fmt, ld);
+        err = qpsk_tx_batch_masked_fmt(ctx, bits, active, npk, out, fmt, ld);
         qpsk_tx_destroy(ctx);
     }
     if (err) return fail(err);
@@ -105,10 +113,11 @@ static int run(int nch, char **paths, char **names, int gap, int host, int fmt) 
 }
 
 int main(int argc, char **argv) {
-    int gap = 903, host = 0, batch = 0, fmt = QPSK_OUT_S16, i = 1;
+    int gap = 903, host = 0, batch = 0, all = 0, fmt = QPSK_OUT_S16, i = 1;
     for (; i < argc && argv[i][0] == '-' && argv[i][1] != 'o'; i++) {
         if (!strcmp(argv[i], "-b")) batch = 1;
         else if (!strcmp(argv[i], "-c")) host = 1;
+        else if (!strcmp(argv[i], "-a")) all = 1;
         else if (!strcmp(argv[i], "-i")) fmt |= QPSK_OUT_INTERLEAVED;
         else if (!strcmp(argv[i], "-g") && i + 1 < argc) gap = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-f") && i + 1 < argc) {
@@ -122,22 +131,22 @@ int main(int argc, char **argv) {
     const int trunk = (fmt & QPSK_OUT_INTERLEAVED) != 0;
     if (!batch && !trunk && argc - i == 2) {
         char *name = argv[i + 1];
-        return run(1, argv + i, &name, gap, host, fmt);
+        return run(1, argv + i, &name, gap, host, fmt, 0);
     }
     if (batch && argc - i >= 3 && !strcmp(argv[argc - 2], "-o")) {
         const int nch = argc - 2 - i;
-        if (trunk) return run(nch, argv + i, &argv[argc - 1], gap, host, fmt);
+        if (trunk) return run(nch, argv + i, &argv[argc - 1], gap, host, fmt, all);
         char **names = calloc((size_t)nch, sizeof(char *));
         for (int c = 0; names && c < nch; c++) {
             names[c] = malloc(strlen(argv[argc - 1]) + 32);
             if (!names[c]) return 1;
             sprintf(names[c], "%s%d.raw", argv[argc - 1], c);
         }
-        return names ? run(nch, argv + i, names, gap, host, fmt) : 1;
+        return names ? run(nch, argv + i, names, gap, host, fmt, all) : 1;
     }
     fprintf(stderr, "usage: %s [-c] [-g GAP] [-f s16|alaw|ulaw] in.bits out.raw\n"
-                    "       %s -b [-c] [-g GAP] [-f s16|alaw|ulaw] in1.bits [in2.bits ...] -o PREFIX\n"
-                    "       %s -b -i [-c] [-g GAP] [-f s16|alaw|ulaw] in1.bits [in2.bits ...] -o TRUNK\n",
+                    "       %s -b [-a] [-c] [-g GAP] [-f s16|alaw|ulaw] in1.bits [in2.bits ...] -o PREFIX\n"
+                    "       %s -b -i [-a] [-c] [-g GAP] [-f s16|alaw|ulaw] in1.bits [in2.bits ...] -o TRUNK\n",
             argv[0], argv[0], argv[0]);
     return 2;
 }

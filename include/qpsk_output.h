@@ -100,6 +100,15 @@ int qpsk_tx_batch_fmt(qpsk_tx_ctx *ctx, const uint8_t *bits, int npackets, void 
 int qpsk_tx_batch_device_fmt(qpsk_tx_ctx *ctx, const uint8_t *d_bits, int npackets, void *d_out,
                              int fmt, long ld, void *stream);
 
+/* qpsk_tx_batch_masked() and qpsk_tx_batch_masked_device() (qpsk_tx.h,
+ * "Channels that come and go") with the written block in format `fmt`, every
+ * format of the two calls above and by the same routes.  An idle slot holds
+ * the encoded zero, as the gap does.  active / d_active NULL: the calls above. */
+int qpsk_tx_batch_masked_fmt(qpsk_tx_ctx *ctx, const uint8_t *bits, const uint8_t *active,
+                             int npackets, void *out, int fmt, long ld);
+int qpsk_tx_batch_masked_device_fmt(qpsk_tx_ctx *ctx, const uint8_t *d_bits, const uint8_t *d_active,
+                                    int npackets, void *d_out, int fmt, long ld, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
  */
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "qpsk_batch.h"
@@ -82,6 +83,103 @@ int qpsk_tx_sync(qpsk_tx_ctx *ctx);
  * QPSK_EINVAL also for NULL st, nch < 1 or gap < 0. */
 int qpsk_tx_batch_host(qpsk_tx_state *st, int nch, const uint8_t *bits, int npackets, int gap,
                        int16_t *out, long ld, int nthreads);
+
+/* Channels that come and go (INTEGRATION.md "Transmit channels that come and
+ * go"): the transmit counterpart of qpsk_rx_reset_channels and
+ * qpsk_rx_state_save/join.
+ *
+ * Own packet index.  Every channel has a 64-bit packet index of its own: the
+ * number of packets of its current stream it has sent.  It is the context's
+ * (qpsk_tx_packets) until one of the calls below gives the channel another
+ * course.  A channel always behaves exactly like a fresh run of the reference
+ * transmitter (src/qpsk.c:278-322 in the order of :380-413) fed its own
+ * packets, and its line carries runs of zeros wherever it was idle.
+ *
+ * Slots.  A call covers npackets slots of P = 1880 + gap samples per channel.
+ *   active  uint8 [nch][npackets]; nonzero = the channel sends in that slot.
+ *           NULL = every slot is active (the plain call).
+ * An active slot holds the 1880 samples of the channel's next packet, bits
+ * row [c][slot]: filtered over the last 9 dibits of the channel's previous
+ * active packet, whatever lies between the two and whether that packet was in
+ * this call or an earlier one (zero filter memory before the channel's first
+ * packet), on the carrier of the channel's own index (1+0i before its first
+ * packet); then gap zeros.  The own index advances by one.
+ * An idle slot holds P zeros (the encoded zero in the G.711 formats, as the gap
+ * does).  Its bits row is not read, and the channel's state, its 9 dibits and
+ * its own index, does not move.
+ * Per row a call writes exactly npackets * P elements, as the plain call does.
+ * qpsk_tx_packets() stays the context's count of slots since create / reset.
+ *
+ * The plain calls (qpsk_tx_batch, _device, and qpsk_output.h's _fmt forms) keep
+ * working after any of the calls below: they mean "every slot active" over the
+ * channels' own indices.  Masked, plain and format calls may alternate, and
+ * calls of 1 + 3 + 1 slots equal one call of 5 with the same mask rows.  A
+ * context that uses none of the calls below (a NULL mask counts as none) is as
+ * before in every respect.
+ *
+ * Errors: every argument check runs before any HIP call.  QPSK_EINVAL for what
+ * the plain calls refuse, for a NULL context, and for c0 < 0, n < 0 or
+ * c0 + n > channels, a NULL out with n > 0, and for qpsk_tx_state_save / _load
+ * n < 1, a NULL buf, size < qpsk_tx_state_size(n), and for _load a snapshot
+ * that is foreign, of another version or of another n.  For
+ * qpsk_tx_reset_channels and qpsk_tx_channel_packets n == 0 is a no-op
+ * returning 0 (they still wait for the calls in flight).  A device allocation
+ * that fails on a call's way out of the uniform state is QPSK_ENOMEM.
+ *
+ *   qpsk_tx_batch_masked(ctx, bits, active, npackets, out, ld)
+ *       qpsk_tx_batch with a mask; host memory, synchronises.
+ *   qpsk_tx_batch_masked_device(ctx, d_bits, d_active, npackets, d_out, ld, stream)
+ *       qpsk_tx_batch_device with a mask in device memory (any address), read
+ *       in stream order on `stream` like d_bits; the call synchronises
+ *       nothing beyond what qpsk_tx_batch_device's contract names (here only
+ *       a call of more slots than any masked one before it, which reallocates
+ *       the per-slot plan).
+ *   qpsk_tx_reset_channels(ctx, c0, n)
+ *       channels [c0, c0 + n) back to the start state (zero filter memory,
+ *       carrier 1+0i) at own index 0; every other channel is untouched.
+ *       Waits for the context's calls in flight.
+ *   qpsk_tx_channel_packets(ctx, c0, n, out)
+ *       out[i] = own index of channel c0 + i.  Waits for the context's calls
+ *       in flight (the indices live on the device once a masked call has run).
+ *   qpsk_tx_state_size(n)
+ *       bytes of a snapshot of n channels: 16 + 12 n; 0 for n < 1.
+ *   qpsk_tx_state_save(ctx, c0, n, buf, size)
+ *       channels [c0, c0 + n) -> buf (host memory, size >= state_size(n)).
+ *   qpsk_tx_state_load(ctx, c0, n, buf, size)
+ *       buf -> channels [c0, c0 + n) of ctx, with the receive side's *join*
+ *       meaning: the channels continue at the snapshot's indices, in a context
+ *       at any other index, with any gap (gap is not state), on any device, in
+ *       any process, while the context's other channels go on.
+ *   Save and load wait for the context's calls in flight.
+ *
+ * Snapshot layout, little endian, version 1:
+ *   offset 0   uint32  magic 0x53585451 ("QTXS")
+ *          4   uint32  version = 1
+ *          8   uint32  n
+ *         12   uint32  0
+ *         16   uint64  own index of channel c0 + i, i = 0 .. n-1
+ *   16 + 8 n   uint32  the channel's last 9 dibits: bit j = I sign (1: -1) of
+ *                      data symbol 239 + j of its latest packet, bit 16 + j its
+ *                      Q sign, j = 0 .. 8; every other bit 0, and the whole word
+ *                      0 when the index is 0
+ * A snapshot is a function of the channels' state alone: equal states give equal
+ * bytes wherever and however they were reached.  qpsk_tx_state_load refuses
+ * words with other bits set and a nonzero word at index 0. */
+int qpsk_tx_batch_masked(qpsk_tx_ctx *ctx, const uint8_t *bits, const uint8_t *active, int npackets,
+                         int16_t *out, long ld);
+int qpsk_tx_batch_masked_device(qpsk_tx_ctx *ctx, const uint8_t *d_bits, const uint8_t *d_active,
+                                int npackets, int16_t *d_out, long ld, void *stream);
+int qpsk_tx_reset_channels(qpsk_tx_ctx *ctx, int c0, int n);
+int qpsk_tx_channel_packets(qpsk_tx_ctx *ctx, int c0, int n, uint64_t *out);
+size_t qpsk_tx_state_size(int n);
+int qpsk_tx_state_save(qpsk_tx_ctx *ctx, int c0, int n, void *buf, size_t size);
+int qpsk_tx_state_load(qpsk_tx_ctx *ctx, int c0, int n, const void *buf, size_t size);
+
+/* The masked call on the host, as qpsk_tx_batch_host is for the plain call:
+ * an idle slot writes P zeros and leaves st[c] alone.  The yardstick of every
+ * GPU result.  active NULL: qpsk_tx_batch_host. */
+int qpsk_tx_batch_masked_host(qpsk_tx_state *st, int nch, const uint8_t *bits, const uint8_t *active,
+                              int npackets, int gap, int16_t *out, long ld, int nthreads);
 
 #ifdef __cplusplus
 }

@@ -172,6 +172,17 @@ def lib():
         L.qpsk_tx_batch_host.argtypes = [vp, i32, vp, i32, i32, vp, C.c_long, i32]
         L.qpsk_tx_state_init.restype = None
         L.qpsk_tx_state_init.argtypes = [vp]
+        L.qpsk_tx_batch_masked.argtypes = [vp, vp, vp, i32, vp, C.c_long]
+        L.qpsk_tx_batch_masked_device.argtypes = [vp, vp, vp, i32, vp, C.c_long, vp]
+        L.qpsk_tx_batch_masked_host.argtypes = [vp, i32, vp, vp, i32, i32, vp, C.c_long, i32]
+        L.qpsk_tx_reset_channels.argtypes = [vp, i32, i32]
+        L.qpsk_tx_channel_packets.argtypes = [vp, i32, i32, vp]
+        L.qpsk_tx_state_size.restype = C.c_size_t
+        L.qpsk_tx_state_size.argtypes = [i32]
+        L.qpsk_tx_state_save.argtypes = [vp, i32, i32, vp, C.c_size_t]
+        L.qpsk_tx_state_load.argtypes = [vp, i32, i32, vp, C.c_size_t]
+        L.qpsk_tx_batch_masked_fmt.argtypes = [vp, vp, vp, i32, vp, i32, C.c_long]
+        L.qpsk_tx_batch_masked_device_fmt.argtypes = [vp, vp, vp, i32, vp, i32, C.c_long, vp]
         L.qpsk_input_bytes.restype = C.c_size_t
         L.qpsk_input_bytes.argtypes = [i32, i32, i32, C.c_long]
         L.qpsk_input_convert_host.argtypes = [i32, vp, C.c_long, i32, i32, vp, i32]
@@ -259,6 +270,9 @@ SYMBOLS = ["qpsk_rx_create", "qpsk_rx_create_mode", "qpsk_rx_mode", "qpsk_rx_des
            "qpsk_tx_create", "qpsk_tx_destroy", "qpsk_tx_reset", "qpsk_tx_channels", "qpsk_tx_gap",
            "qpsk_tx_packets", "qpsk_tx_batch", "qpsk_tx_batch_device", "qpsk_tx_sync",
            "qpsk_tx_batch_host",
+           "qpsk_tx_batch_masked", "qpsk_tx_batch_masked_device", "qpsk_tx_batch_masked_host",
+           "qpsk_tx_reset_channels", "qpsk_tx_channel_packets", "qpsk_tx_state_size", "qpsk_tx_state_save",
+           "qpsk_tx_state_load", "qpsk_tx_batch_masked_fmt", "qpsk_tx_batch_masked_device_fmt",
            "qpsk_input_bytes", "qpsk_input_convert_host", "qpsk_input_convert_device",
            "qpsk_rx_batch_fmt", "qpsk_rx_batch_device_fmt", "qpsk_stream_create_fmt",
            "qpsk_stream_acquire_raw",
@@ -1178,6 +1192,32 @@ def _tx_bits_tensor(bits, nch: int) -> int:
     return bits.shape[1]
 
 
+def _tx_mask(active, nch: int, npk: int):
+    """A host call's mask: None, or uint8 [nch][npackets] (nonzero = the
+    channel sends in that slot; any other dtype is compared with 0)."""
+    if active is None:
+        return None
+    active = np.asarray(active)
+    if active.dtype != np.uint8:
+        active = active != 0
+    active = np.ascontiguousarray(active, dtype=np.uint8)
+    if active.shape != (nch, npk):
+        raise ValueError(f"active must be [{nch}][{npk}], got {active.shape}")
+    return active
+
+
+def _tx_mask_tensor(active, nch: int, npk: int):
+    """A device call's mask: None, or a contiguous cuda uint8 / bool tensor
+    [nch][npackets] (any address)."""
+    import torch
+    if active is None:
+        return None
+    if active.dtype not in (torch.uint8, torch.bool) or tuple(active.shape) != (nch, npk) \
+            or not active.is_contiguous() or not active.is_cuda:
+        raise ValueError(f"active must be a contiguous cuda uint8 or bool [{nch}][{npk}] tensor")
+    return active.view(torch.uint8)
+
+
 class Transmitter:
     """A batch of ``nch`` independent transmitters on one GPU (``qpsk_tx_ctx``,
     include/qpsk_tx.h).
@@ -1187,6 +1227,13 @@ class Transmitter:
     samples follow every packet.  State persists across calls.  Like
     ``Receiver`` there is no CPU fallback: without a GPU the constructor raises
     (``tx_batch_host`` is the explicit host path).
+
+    Channels may come and go (include/qpsk_tx.h "Channels that come and go"):
+    every ``modulate*`` takes ``active``, [nch][npackets], nonzero where the
+    channel sends in that slot (None: every slot); an idle slot is 1880 + gap
+    zeros and leaves the channel's state alone.  ``reset_channels`` starts
+    channels afresh, ``state_save`` / ``state_load`` move them to another
+    transmitter, ``channel_packets`` reads their own packet indices.
     """
 
     def __init__(self, nch: int, device: int = 0, gap: int = 903):
@@ -1212,56 +1259,97 @@ class Transmitter:
     def packets(self) -> int:
         return int(lib().qpsk_tx_packets(self._h))
 
-    def modulate(self, bits) -> np.ndarray:
-        """Host arrays: bits uint8 [nch][npackets][8][62] -> int16
-        [nch][npackets * (1880 + gap)]."""
-        bits = _tx_bits(bits, self.nch)
-        npk = bits.shape[1]
-        out = np.zeros((self.nch, npk * (TX_PACKET + self.gap)), np.int16)
-        _check(lib().qpsk_tx_batch(self._h, _ptr(bits), npk, _ptr(out), out.shape[1]))
+    def reset_channels(self, c0: int, n: int = 1) -> None:
+        """Channels [c0, c0 + n) back to the start state, at own packet index
+        0; every other channel is untouched (qpsk_tx_reset_channels)."""
+        _check(lib().qpsk_tx_reset_channels(self._h, c0, n))
+
+    def channel_packets(self, c0: int = 0, n: int | None = None) -> np.ndarray:
+        """The own packet index of channels [c0, c0 + n), uint64 [n]
+        (qpsk_tx_channel_packets); ``packets`` stays the context's."""
+        n = self.nch - c0 if n is None else n
+        out = np.zeros(max(n, 0), np.uint64)
+        _check(lib().qpsk_tx_channel_packets(self._h, c0, n, _ptr(out)))
         return out
 
-    def modulate_device(self, bits, out, stream=None) -> None:
+    def state_save(self, c0: int = 0, n: int | None = None) -> bytes:
+        """Snapshot of channels [c0, c0 + n) (qpsk_tx_state_save): their own
+        packet indices and last 9 dibits, as bytes."""
+        n = self.nch - c0 if n is None else n
+        buf = np.zeros(int(lib().qpsk_tx_state_size(n)), np.uint8)
+        _check(lib().qpsk_tx_state_save(self._h, c0, n, _ptr(buf), buf.size))
+        return buf.tobytes()
+
+    def state_load(self, snap: bytes, c0: int = 0, n: int | None = None) -> None:
+        """Load a snapshot of n channels (default: as many as it holds), taken
+        at any packet index and gap, into channels [c0, c0 + n) while the
+        others go on (qpsk_tx_state_load)."""
+        buf = np.frombuffer(snap, np.uint8)
+        if n is None:
+            if len(snap) < 16:
+                _check(QPSK_EINVAL)
+            n = int(np.frombuffer(snap[8:12], "<u4")[0])
+        _check(lib().qpsk_tx_state_load(self._h, c0, n, _ptr(buf), buf.size))
+
+    def modulate(self, bits, active=None) -> np.ndarray:
+        """Host arrays: bits uint8 [nch][npackets][8][62] -> int16
+        [nch][npackets * (1880 + gap)]; ``active`` [nch][npackets] marks the
+        slots a channel sends in (qpsk_tx_batch_masked)."""
+        bits = _tx_bits(bits, self.nch)
+        npk = bits.shape[1]
+        active = _tx_mask(active, self.nch, npk)
+        out = np.zeros((self.nch, npk * (TX_PACKET + self.gap)), np.int16)
+        _check(lib().qpsk_tx_batch_masked(self._h, _ptr(bits), _ptr(active), npk, _ptr(out), out.shape[1]))
+        return out
+
+    def modulate_device(self, bits, out, stream=None, active=None) -> None:
         """Device tensors (torch, on this device): bits uint8 [nch][npackets][8][62]
         contiguous, out int16 [nch][>= npackets * (1880 + gap)] with unit stride
         along a row and ld = out.stride(0).  Enqueues on ``stream`` (default:
-        torch's current stream) and returns without synchronising."""
+        torch's current stream) and returns without synchronising.  ``active``
+        is a cuda uint8 or bool tensor [nch][npackets], read in stream order
+        (qpsk_tx_batch_masked_device)."""
         import torch
         npk = _tx_bits_tensor(bits, self.nch)
+        active = _tx_mask_tensor(active, self.nch, npk)
         if out.dtype != torch.int16 or out.dim() != 2 or out.shape[0] != self.nch or not out.is_cuda \
                 or out.shape[1] < npk * (TX_PACKET + self.gap) \
                 or (out.shape[1] > 1 and out.stride(1) != 1):
             raise ValueError("out must be a cuda int16 [nch][>= npackets * (1880 + gap)] tensor "
                              "with unit stride along a row")
         ld = out.stride(0) if self.nch > 1 else max(out.stride(0), out.shape[1])
-        _check(lib().qpsk_tx_batch_device(self._h, _ptr(bits), npk, _ptr(out), ld, _stream(stream, out.device)))
+        _check(lib().qpsk_tx_batch_masked_device(self._h, _ptr(bits), _ptr(active), npk, _ptr(out), ld,
+                                                 _stream(stream, out.device)))
 
-    def modulate_fmt(self, bits, fmt: int, ld: int | None = None, out=None) -> np.ndarray:
+    def modulate_fmt(self, bits, fmt: int, ld: int | None = None, out=None, active=None) -> np.ndarray:
         """``modulate`` with the block in format ``fmt`` (OUT_*): uint8 G.711
         codes or int16, planar [nch][ld >= n] or interleaved [n][ld >= nch],
         n = npackets * (1880 + gap); ld None = the minimum.  Only the block's
         bytes cross PCIe and are written (qpsk_tx_batch_fmt): with ``out``
         given, a contiguous array of that shape, its row tails and foreign
-        columns keep their contents; otherwise they are zero."""
+        columns keep their contents; otherwise they are zero.  ``active`` as
+        in ``modulate`` (qpsk_tx_batch_masked_fmt)."""
         bits = _tx_bits(bits, self.nch)
         npk = bits.shape[1]
+        active = _tx_mask(active, self.nch, npk)
         rows, ld = _out_shape(fmt, self.nch, npk * (TX_PACKET + self.gap), ld)
         out = _out_array(out, fmt, rows, ld)
-        _check(lib().qpsk_tx_batch_fmt(self._h, _ptr(bits), npk, _ptr(out), fmt, ld))
+        _check(lib().qpsk_tx_batch_masked_fmt(self._h, _ptr(bits), _ptr(active), npk, _ptr(out), fmt, ld))
         return out
 
-    def modulate_device_fmt(self, bits, out, fmt: int, ld: int | None = None, stream=None) -> None:
+    def modulate_device_fmt(self, bits, out, fmt: int, ld: int | None = None, stream=None, active=None) -> None:
         """``modulate_device`` with the block in format ``fmt`` (OUT_*): ``out``
         is a cuda tensor [nch][>= n] (planar) or [n][>= nch] (interleaved) of
         uint8 codes or int16, unit stride along a row; ``ld`` defaults to its
-        row stride.  The conversion follows the modulator on ``stream``
-        (qpsk_tx_batch_device_fmt)."""
+        row stride.  The conversion follows the modulator on ``stream``.
+        ``active`` as in ``modulate_device`` (qpsk_tx_batch_masked_device_fmt)."""
         npk = _tx_bits_tensor(bits, self.nch)
+        active = _tx_mask_tensor(active, self.nch, npk)
         _out_shape(fmt, self.nch, npk * (TX_PACKET + self.gap), None)
         row = _torch_out(out, fmt, self.nch, npk * (TX_PACKET + self.gap))
         ld = row if ld is None else int(ld)
-        _check(lib().qpsk_tx_batch_device_fmt(self._h, _ptr(bits), npk, _ptr(out), fmt, ld,
-                                              _stream(stream, out.device)))
+        _check(lib().qpsk_tx_batch_masked_device_fmt(self._h, _ptr(bits), _ptr(active), npk, _ptr(out), fmt, ld,
+                                                     _stream(stream, out.device)))
 
 
 def tx_states(nch: int) -> np.ndarray:
@@ -1273,13 +1361,16 @@ def tx_states(nch: int) -> np.ndarray:
     return st
 
 
-def tx_batch_host(bits, gap: int = 903, states=None, threads: int = 0) -> np.ndarray:
+def tx_batch_host(bits, gap: int = 903, states=None, threads: int = 0, active=None) -> np.ndarray:
     """qpsk_tx_batch_host: the batched transmitter's contract on the host.
     bits uint8 [nch][npackets][8][62] -> int16 [nch][npackets * (1880 + gap)].
     ``states`` (tx_states(nch)) is advanced in place, so a stream may continue
-    over calls; None starts every channel fresh."""
+    over calls; None starts every channel fresh.  ``active`` [nch][npackets]
+    marks the slots a channel sends in (qpsk_tx_batch_masked_host): an idle
+    slot is zeros and leaves the channel's state alone."""
     bits = _tx_bits(bits)
     nch, npk = bits.shape[:2]
+    active = _tx_mask(active, nch, npk)
     if states is None:
         states = tx_states(nch)
     if states.dtype != np.uint8 or states.shape != (nch, TX_STATE_SIZE) or not states.flags.c_contiguous:
@@ -1287,8 +1378,8 @@ def tx_batch_host(bits, gap: int = 903, states=None, threads: int = 0) -> np.nda
     if gap < 0:
         _check(QPSK_EINVAL)
     out = np.zeros((nch, npk * (TX_PACKET + gap)), np.int16)
-    _check(lib().qpsk_tx_batch_host(_ptr(states), nch, _ptr(bits), npk, gap, _ptr(out),
-                                    out.shape[1], _threads(threads)))
+    _check(lib().qpsk_tx_batch_masked_host(_ptr(states), nch, _ptr(bits), _ptr(active), npk, gap, _ptr(out),
+                                           out.shape[1], _threads(threads)))
     return out
 
 

@@ -271,12 +271,11 @@ int tx_fmt_check(const qpsk_tx_ctx* c, const void* bits, int npackets, const voi
 // the modulator's rows in the context's buffer start 16-byte aligned
 long conv_ld(long N) { return (N + 7) & ~7L; }
 
-}  // namespace
-
-extern "C" int qpsk_tx_batch_device_fmt_path(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets, void* d_out,
-                                             int fmt, long ld, void* stream, int path) {
+// qpsk_tx_batch_masked_device_fmt on a chosen path; d_active NULL = the plain call
+int tx_device_fmt(qpsk_tx_ctx* c, const uint8_t* d_bits, const uint8_t* d_active, int npackets, void* d_out,
+                  int fmt, long ld, void* stream, int path) {
     if (fmt == (QPSK_OUT_S16 | QPSK_OUT_PLANAR))
-        return qpsk_tx_batch_device(c, d_bits, npackets, static_cast<int16_t*>(d_out), ld, stream);
+        return qpsk_tx_batch_masked_device(c, d_bits, d_active, npackets, static_cast<int16_t*>(d_out), ld, stream);
     long N = 0;
     const int chk = tx_fmt_check(c, d_bits, npackets, d_out, fmt, ld, &N);
     const bool fusable = QPSK_FMT_LAYOUT(fmt) == QPSK_OUT_PLANAR && QPSK_FMT_ENC(fmt) != QPSK_OUT_S16;
@@ -285,27 +284,44 @@ extern "C" int qpsk_tx_batch_device_fmt_path(qpsk_tx_ctx* c, const uint8_t* d_bi
         return QPSK_EINVAL;
     if (chk != QPSK_OK || npackets == 0) return chk;
     if (path == QPSK_OUT_PATH_FUSED)   // the modulator's store pass writes the codes
-        return qpsk_tx_batch_device_enc(c, d_bits, npackets, d_out, ld, stream, QPSK_FMT_ENC(fmt));
+        return qpsk_tx_batch_masked_device_enc(c, d_bits, d_active, npackets, d_out, ld, stream, QPSK_FMT_ENC(fmt));
     const int nch = qpsk_tx_channels(c);
     const long sld = conv_ld(N);
     int16_t* conv = nullptr;
     int r = qpsk_tx_fmt_conv(c, (size_t)nch * (size_t)sld, &conv);
     if (r != QPSK_OK) return r;
-    r = qpsk_tx_batch_device(c, d_bits, npackets, conv, sld, stream);
+    r = qpsk_tx_batch_masked_device(c, d_bits, d_active, npackets, conv, sld, stream);
     if (r != QPSK_OK) return r;
     r = qpsk_output_convert_device(fmt, conv, sld, nch, N, d_out, ld, stream);
     if (r != QPSK_OK) return r;
     return qpsk_tx_mark(c, stream);
 }
 
+}  // namespace
+
+extern "C" int qpsk_tx_batch_device_fmt_path(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets, void* d_out,
+                                             int fmt, long ld, void* stream, int path) {
+    return tx_device_fmt(c, d_bits, nullptr, npackets, d_out, fmt, ld, stream, path);
+}
+
 extern "C" int qpsk_tx_batch_device_fmt(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets, void* d_out, int fmt,
                                         long ld, void* stream) {
-    return qpsk_tx_batch_device_fmt_path(c, d_bits, npackets, d_out, fmt, ld, stream, QPSK_OUT_PATH_DEFAULT);
+    return tx_device_fmt(c, d_bits, nullptr, npackets, d_out, fmt, ld, stream, QPSK_OUT_PATH_DEFAULT);
+}
+
+extern "C" int qpsk_tx_batch_masked_device_fmt(qpsk_tx_ctx* c, const uint8_t* d_bits, const uint8_t* d_active,
+                                               int npackets, void* d_out, int fmt, long ld, void* stream) {
+    return tx_device_fmt(c, d_bits, d_active, npackets, d_out, fmt, ld, stream, QPSK_OUT_PATH_DEFAULT);
 }
 
 extern "C" int qpsk_tx_batch_fmt(qpsk_tx_ctx* c, const uint8_t* bits, int npackets, void* out, int fmt, long ld) {
+    return qpsk_tx_batch_masked_fmt(c, bits, nullptr, npackets, out, fmt, ld);
+}
+
+extern "C" int qpsk_tx_batch_masked_fmt(qpsk_tx_ctx* c, const uint8_t* bits, const uint8_t* active, int npackets,
+                                        void* out, int fmt, long ld) {
     if (fmt == (QPSK_OUT_S16 | QPSK_OUT_PLANAR))
-        return qpsk_tx_batch(c, bits, npackets, static_cast<int16_t*>(out), ld);
+        return qpsk_tx_batch_masked(c, bits, active, npackets, static_cast<int16_t*>(out), ld);
     long N = 0;
     const int chk = tx_fmt_check(c, bits, npackets, out, fmt, ld, &N);
     if (chk != QPSK_OK || npackets == 0) return chk;
@@ -320,11 +336,15 @@ extern "C" int qpsk_tx_batch_fmt(qpsk_tx_ctx* c, const uint8_t* bits, int npacke
     // the block on the device is dense: rows of `width` bytes, `rows` of them
     const size_t width = (inter ? (size_t)nch : (size_t)N) * es, rows = inter ? (size_t)N : (size_t)nch;
     const size_t nbits = (size_t)nch * (size_t)npackets * QPSK_TX_PACKET_BITS;
-    qhip::DevBuf<uint8_t> d_bits, d_block;   // released on return, after the synchronisation
+    const size_t nact = active ? (size_t)nch * (size_t)npackets : 0;
+    qhip::DevBuf<uint8_t> d_bits, d_active, d_block;   // released on return, after the synchronisation
     int r = herr(d_bits.reserve(nbits));
+    if (r == QPSK_OK) r = herr(d_active.reserve(nact));
     if (r == QPSK_OK) r = herr(d_block.reserve(width * rows));
     if (r == QPSK_OK) r = herr(hipMemcpyAsync(d_bits, bits, nbits, hipMemcpyHostToDevice, s));
-    if (r == QPSK_OK) r = qpsk_tx_batch_device_fmt(c, d_bits, npackets, d_block, fmt, inter ? (long)nch : N, s);
+    if (r == QPSK_OK && active) r = herr(hipMemcpyAsync(d_active, active, nact, hipMemcpyHostToDevice, s));
+    if (r == QPSK_OK)
+        r = qpsk_tx_batch_masked_device_fmt(c, d_bits, d_active, npackets, d_block, fmt, inter ? (long)nch : N, s);
     // only the block's bytes come back: the caller's row tails and foreign columns keep their contents
     if (r == QPSK_OK) {
         if ((size_t)ld * es == width)

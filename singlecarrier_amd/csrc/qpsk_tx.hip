@@ -37,6 +37,18 @@
 // 16 bytes are stored per int16.  The same kernel writes the planar G.711
 // formats of include/qpsk_output.h: its store pass compresses a lane's 8
 // samples into one aligned 8-byte store (heads and tails per code).
+//
+// Channels that come and go (qpsk_tx.h).  The above is the *uniform* context:
+// every channel at the context's packet count.  Once a channel has an index of
+// its own (qpsk_tx_reset_channels, qpsk_tx_state_load, a call with a mask) the
+// context is *general* until qpsk_tx_reset: the indices live on the device, a
+// pre-pass (tx_plan_kernel) walks each channel's slots once and writes one plan
+// word per channel and slot, and tx_mask_kernel, tx_batch_kernel's tiling with
+// everything that was per period now per period, channel and slot, modulates
+// from the plan.  The carrier needs no recurrence there: from packet 8 on each
+// packet's carrier is the exact negation of the one before (DESIGN.md "The
+// carrier's period"), so own index p reads row min(p, 8) of a 9-packet table
+// uploaded once per context, negated for odd p > 8.
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -71,6 +83,20 @@ constexpr int kSignWords = kSignBits / 32 + 1;  // + one zero word: a window rea
 static_assert(kTile / 5 + 2 <= kRounds * kThreads, "a tile's periods must fit the rounds");
 static_assert(kTile / 5 + 2 + kHist <= kSignBits, "and their symbols the bit strings");
 static_assert(kMargin >= 4 && kMargin % kChunk == 0, "margin keeps the 16-byte LDS reads aligned");
+
+// The plan word of a channel's slot (tx_plan_kernel -> tx_mask_kernel).  The 9
+// history dibits ride in the word itself, in the saved state's layout (bit j =
+// I sign, bit 16 + j = Q sign), so the modulator never chases where they came
+// from: an earlier slot of the call, the saved word, or none (kPlanStart).
+constexpr uint32_t kDibits = 0x01ff01ffu;
+constexpr uint32_t kPlanActive = 1u << 31;   // the channel sends in this slot
+constexpr uint32_t kPlanStart = 1u << 30;    // its first packet: zero filter memory
+constexpr uint32_t kPlanNeg = 1u << 29;      // carrier = minus the table row
+constexpr int kPlanRowShift = 25;            // carrier row 0 .. 8, 4 bits
+constexpr int kCarrierRows = 9;              // packets 0 .. 7 are a transient, 8 repeats negated
+constexpr int kPlanSlots = 4;                // slots a tile's periods and their history touch
+static_assert((kSymPacket - 1 + kTile / 5 + 2) / kSymPacket + 2 <= kPlanSlots,
+              "a tile's last period lies at most 2 slots past its first, and reads the slot after");
 
 // bit u set: preamble symbol u is -1 (both components, src/qpsk.c:361-365)
 constexpr unsigned long long pre_neg(int half) {
@@ -301,6 +327,232 @@ tx_state_kernel(const uint8_t* __restrict__ bits, uint32_t* __restrict__ state, 
     state[c] = st;
 }
 
+// data symbols 239..247 of a packet as a state word
+__device__ inline uint32_t last_dibits(const uint8_t* __restrict__ packet) {
+    const uint8_t* p = packet + 2 * (kSymPacket - QK_NPRE - kHist);
+    uint32_t st = 0;
+    for (int j = 0; j < kHist; j++) {
+        st |= (uint32_t)(p[2 * j + 1] == 1) << j;
+        st |= (uint32_t)(p[2 * j] == 1) << (16 + j);
+    }
+    return st;
+}
+
+// The plan pre-pass of a general context: a lane walks its channel's npk mask
+// bytes once (active == nullptr: every slot active), writes the plan word of
+// every slot, slot-major so that the lanes' stores lie side by side, and
+// leaves the channel's new saved dibits and own index.  It takes the place of
+// tx_state_kernel on this path.  Plain stores, no atomics, no block waits for
+// another.
+__global__ void __launch_bounds__(kThreads)
+tx_plan_kernel(const uint8_t* __restrict__ bits, const uint8_t* __restrict__ active,
+               uint32_t* __restrict__ state, uint64_t* __restrict__ index, uint32_t* __restrict__ plan,
+               int nch, int npk) {
+    const long c = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (c >= nch) return;
+    uint64_t idx = index[c];
+    uint32_t st = idx ? state[c] & kDibits : 0u;   // the word of a reset context may be stale
+    for (int k = 0; k < npk; k++) {
+        uint32_t w = 0;
+        if (!active || active[(size_t)c * npk + k]) {
+            const uint32_t row = idx < (uint64_t)(kCarrierRows - 1) ? (uint32_t)idx : (uint32_t)(kCarrierRows - 1);
+            w = kPlanActive | (row << kPlanRowShift) | st;
+            if (idx == 0) w |= kPlanStart;
+            if (idx >= (uint64_t)kCarrierRows && (idx & 1)) w |= kPlanNeg;
+            st = last_dibits(bits + ((size_t)c * npk + (size_t)k) * kPacketBits);
+            idx++;
+        }
+        plan[(size_t)k * nch + c] = w;
+    }
+    state[c] = st;
+    index[c] = idx;
+}
+
+// leaving the uniform state: every channel's own index is the context's count
+__global__ void __launch_bounds__(kThreads)
+tx_seed_kernel(uint64_t* __restrict__ index, int nch, uint64_t packets) {
+    const long c = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (c < nch) index[c] = packets;
+}
+
+// tx_batch_kernel for a general context: the same tiles, classes, channel
+// loop, LDS tile and store pass.  What was independent of the channel per
+// period is now read per channel: a slot's plan word says whether the channel
+// sends there (an idle slot's periods are written as zeros: the tile's two
+// buffers are reused over the channel loop), whether the packet is the
+// channel's first (the `live` mask of its first 9 periods), and which carrier
+// row and sign it rides; the 5 carrier values come from the 9-row table (135 KB,
+// resident in L2) instead of registers.  A packet's history symbols are the
+// dibits of its own plan word, never the slot in front of it.
+template <int ENC, typename E>
+__global__ void __launch_bounds__(kThreads)
+tx_mask_kernel(const uint8_t* __restrict__ bits, const uint32_t* __restrict__ plan,
+               const float2* __restrict__ tab, E* __restrict__ out, long ld, int nch, int npk, int gap,
+               long tile0) {
+    static_assert(sizeof(E) == (ENC == QPSK_OUT_S16 ? 2 : 1), "the element of the encoding");
+    __shared__ __attribute__((aligned(16))) int16_t tile[2][kTile + 2 * kMargin];
+    __shared__ uint32_t sgn[kLoop][2][kSignWords];
+    __shared__ uint32_t planw[kLoop][kPlanSlots];   // slots k0 .. k0 + 3 of each channel, 0 past the call
+    const int tid = threadIdx.x;
+    const int cls = blockIdx.x & (kClasses - 1);
+    const long cbase = cls + (long)kClasses * kLoop * (blockIdx.x / kClasses);
+    if (cbase >= nch) return;
+    const int nloop = (int)lmin((long)kLoop, (nch - cbase + kClasses - 1) / kClasses);
+    const long P = (long)kTxPacket + gap;
+    const long N = (long)npk * P;
+    const unsigned a = (unsigned)(((uintptr_t)out / sizeof(E)) + (uint64_t)cbase * (uint64_t)ld) & (kChunk - 1);
+    const long pl0 = (tile0 + blockIdx.y) * kTile - (long)a;   // the tile is [pl0, pl0 + kTile)
+    const long pl = pl0 > 0 ? pl0 : 0, pe = lmin(pl0 + kTile, N);
+    if (pl >= pe) return;
+    // as in tx_batch_kernel: every slot counts its 1880 TX samples, sent or not
+    const long kl = pl / P, ke = pe / P;
+    const long tlo = kl * kTxPacket + lmin(pl - kl * P, (long)kTxPacket);
+    const long thi = ke * kTxPacket + lmin(pe - ke * P, (long)kTxPacket);
+    const long slo = tlo / 5;
+    const int nper = thi > tlo ? (int)((thi + 4) / 5 - slo) : 0;
+    const long k0 = slo / kSymPacket;
+    const int u0 = (int)(slo - k0 * kSymPacket);
+
+    for (int i = tid; i < (int)(sizeof(tile) / sizeof(uint32_t)); i += kThreads)
+        reinterpret_cast<uint32_t*>(&tile[0][0])[i] = 0u;
+    for (int i = tid; i < (int)(sizeof(sgn) / sizeof(uint32_t)); i += kThreads)
+        (&sgn[0][0][0])[i] = 0u;
+    if (tid < kLoop * kPlanSlots) {
+        const int i = tid / kPlanSlots, j = tid % kPlanSlots;
+        const long k = k0 + j;
+        planw[i][j] = i < nloop && k < npk ? plan[(size_t)k * nch + (size_t)(cbase + (long)kClasses * i)] : 0u;
+    }
+    __syncthreads();
+    // sign bits: bit b of a channel's strings is symbol slo - 9 + b of the slots'
+    // common time.  The last 9 symbols of a slot serve the next slot's first
+    // periods as history, so there the next slot's plan word decides: its
+    // dibits when that slot is active, else the slot's own payload.
+    const int ngrp = (nper + kHist + 63) >> 6;
+    const int nitem = nloop * ngrp;
+    auto fetch = [&](int item, bool& neg_i, bool& neg_q) {
+        neg_i = neg_q = false;
+        if (item >= nitem) return;
+        const int i = item / ngrp, b = (item - i * ngrp) * 64 + (tid & 63);
+        if (b >= nper + kHist) return;
+        const long c = cbase + (long)kClasses * i;
+        const int rel = u0 - kHist + b;                // symbol of slot k0, or its neighbours
+        const int dk = rel < 0 ? -1 : rel / kSymPacket;
+        const int u = rel - dk * kSymPacket;
+        if (u >= kSymPacket - kHist) {
+            const uint32_t wn = planw[i][dk + 1];
+            if (wn & kPlanActive) {
+                const int j = u - (kSymPacket - kHist);
+                neg_i = (wn >> j) & 1u;
+                neg_q = (wn >> (j + 16)) & 1u;
+                return;
+            }
+        }
+        if (dk < 0 || !(planw[i][dk] & kPlanActive)) return;   // idle: its bits row is not read
+        if (u < QK_NPRE) {
+            constexpr unsigned long long lo = pre_neg(0), hi = pre_neg(1);
+            neg_i = neg_q = ((u < 64 ? lo : hi) >> (u & 63)) & 1ull;
+        } else {
+            const uint8_t* p = bits + ((size_t)c * npk + (size_t)(k0 + dk)) * kPacketBits +
+                               2 * (u - QK_NPRE);
+            neg_q = p[0] == 1;
+            neg_i = p[1] == 1;
+        }
+    };
+    constexpr int kWaves = kThreads / 64, kFetch = 4;
+    for (int it = tid >> 6; it < nitem; it += kWaves * kFetch) {
+        bool ni[kFetch], nq[kFetch];
+#pragma unroll
+        for (int f = 0; f < kFetch; f++) fetch(it + f * kWaves, ni[f], nq[f]);
+#pragma unroll
+        for (int f = 0; f < kFetch; f++) {
+            const int item = it + f * kWaves;
+            const unsigned long long mi = __ballot(ni[f]), mq = __ballot(nq[f]);
+            if ((tid & 63) == 0 && item < nitem) {
+                const int i = item / ngrp, w = (item - i * ngrp) * 2;
+                sgn[i][0][w] = (uint32_t)mi;
+                sgn[i][0][w + 1] = (uint32_t)(mi >> 32);
+                sgn[i][1][w] = (uint32_t)mq;
+                sgn[i][1][w + 1] = (uint32_t)(mq >> 32);
+            }
+        }
+    }
+
+    // per period, independent of the channel: where it lies, not what it carries
+    float scale[kRounds];
+    int slot[kRounds], sym[kRounds], dks[kRounds];
+#pragma unroll
+    for (int rd = 0; rd < kRounds; rd++) {
+        const int n = tid + rd * kThreads;
+        scale[rd] = 0.0f;
+        slot[rd] = sym[rd] = dks[rd] = 0;
+        if (n < nper) {
+            const int rel = u0 + n;
+            const int dk = rel / kSymPacket;
+            const int u = rel - dk * kSymPacket;
+            const long p = (k0 + dk) * P + 5 * u;
+            slot[rd] = (int)(p - pl0) + kMargin;       // in [kMargin - 4, kMargin + kTile)
+            scale[rd] = u < QK_NPRE ? 8192.0f : 16384.0f;
+            sym[rd] = u;
+            dks[rd] = dk;
+        }
+    }
+    const long p0 = pl0 + (long)tid * kChunk;          // this lane's 8 samples in the store pass
+    const bool whole = p0 >= 0 && p0 + kChunk <= N;
+    __syncthreads();
+
+    for (int i = 0; i < nloop; i++) {
+        int16_t* buf = tile[i & 1];
+#pragma unroll
+        for (int rd = 0; rd < kRounds; rd++) {
+            const int n = tid + rd * kThreads;
+            if (n >= nper) continue;
+            int16_t* dst = buf + slot[rd];
+            const uint32_t w = planw[i][dks[rd]];
+            if (!(w & kPlanActive)) {                  // an idle slot: the buffer held another channel
+#pragma unroll
+                for (int jj = 0; jj < 5; jj++) dst[jj] = 0;
+                continue;
+            }
+            // A negated carrier negates sr exactly (both products change sign, and
+            // so does their rounded difference), and (-sr) * scale is sr * -scale
+            // bit for bit: the sign rides the scale.
+            const float2* tp = tab + ((w >> kPlanRowShift) & 15u) * (uint32_t)kTxPacket + 5 * sym[rd];
+            const float sc = (w & kPlanNeg) ? -scale[rd] : scale[rd];
+            float2 ph[5];
+#pragma unroll
+            for (int jj = 0; jj < 5; jj++) ph[jj] = tp[jj];
+            const uint32_t* wi = sgn[i][0];
+            const uint32_t* wq = sgn[i][1];
+            const uint32_t bi = __funnelshift_r(wi[n >> 5], wi[(n >> 5) + 1], n & 31);
+            const uint32_t bq = __funnelshift_r(wq[n >> 5], wq[(n >> 5) + 1], n & 31);
+            if ((w & kPlanStart) && sym[rd] < kHist)   // the stream's first 45 samples
+                period<true>(bi, bq, 0x3ffu & (0x3ffu << (kHist - sym[rd])), ph, sc, dst);
+            else
+                period<false>(bi, bq, 0x3ffu, ph, sc, dst);
+        }
+        __syncthreads();   // one barrier per channel: the other buffer's readers passed the last one
+        E* row = out + (size_t)(cbase + (long)kClasses * i) * (size_t)ld;
+        const int16_t* src = buf + kMargin + tid * kChunk;
+        if constexpr (ENC == QPSK_OUT_S16) {
+            if (whole) {
+                *reinterpret_cast<uint4*>(row + p0) = *reinterpret_cast<const uint4*>(src);
+            } else {
+                for (int e = 0; e < kChunk; e++)
+                    if (p0 + e >= 0 && p0 + e < N) row[p0 + e] = src[e];
+            }
+        } else {
+            if (whole) {
+                const uint4 v = *reinterpret_cast<const uint4*>(src);
+                *reinterpret_cast<uint2*>(row + p0) = make_uint2(qfmt::encode4<ENC>(v.x, v.y), qfmt::encode4<ENC>(v.z, v.w));
+            } else {
+                for (int e = 0; e < kChunk; e++)
+                    if (p0 + e >= 0 && p0 + e < N)
+                        row[p0 + e] = (uint8_t)qfmt::encode<ENC>(src[e]);
+            }
+        }
+    }
+}
+
 // an allocation the device refused is QPSK_ENOMEM to the transmitter's callers
 int enomem(int r) { return r == QPSK_EHIP - (int)hipErrorOutOfMemory ? QPSK_ENOMEM : r; }
 
@@ -322,6 +574,15 @@ struct qpsk_tx_ctx {
     // the modulator's int16 block of calls in another output format
     // (qpsk_output.hip on qpsk_tx_fmt_conv); empty until such a call
     qhip::DevBuf<int16_t> d_conv;
+    // Channels that come and go.  uniform: every channel at `packets`, the
+    // per-call carrier table and tx_batch_kernel.  Otherwise the own indices
+    // are d_index, and the calls go through tx_plan_kernel and tx_mask_kernel.
+    // All of it stays empty on a context that never leaves the uniform state.
+    bool uniform = true;
+    qhip::DevBuf<uint64_t> d_index;   // [nch] own packet index
+    qhip::DevBuf<float2> d_rows;      // the 9 carrier rows, uploaded once
+    qhip::PinBuf<float> h_rows;       // their staging: an upload may still be pending
+    qhip::DevBuf<uint32_t> d_plan;    // [npackets][nch] plan words of the current call
 };
 
 extern "C" qpsk_tx_ctx* qpsk_tx_create(int device, int nch, int gap, int* err) {
@@ -368,6 +629,7 @@ extern "C" int qpsk_tx_reset(qpsk_tx_ctx* c) {
     c->packets = 0;   // the saved dibits are not read before the first packet
     c->phase[0] = 1.0f;
     c->phase[1] = 0.0f;
+    c->uniform = true;   // own indices are seeded again when the context next leaves this state
     return QPSK_OK;
 }
 
@@ -406,16 +668,63 @@ static int tx_check(const qpsk_tx_ctx* c, const void* bits, int npackets, const 
     return QPSK_OK;
 }
 
-// qpsk_tx_batch_device with the element the store pass writes named: d_out is
-// int16 [nch][ld] for QPSK_OUT_S16 and uint8 [nch][ld] G.711 codes for
-// QPSK_OUT_ALAW / QPSK_OUT_ULAW (qpsk_tx_internal.h)
-extern "C" int qpsk_tx_batch_device_enc(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets, void* d_out,
-                                        long ld, void* stream, int enc) {
-    if (enc != QPSK_OUT_S16 && enc != QPSK_OUT_ALAW && enc != QPSK_OUT_ULAW) return QPSK_EINVAL;
-    const int chk = tx_check(c, d_bits, npackets, d_out, ld);
-    if (chk != QPSK_OK || npackets == 0) return chk;
-    hipStream_t s = (hipStream_t)stream;
-    HCHECK(hipSetDevice(c->device));
+static dim3 chan_grid(int nch) { return dim3((unsigned)((nch + kThreads - 1) / kThreads)); }
+
+// Leaving the uniform state, in stream order on s: the carrier rows (once per
+// context) and every channel's own index = the context's count.
+static int tx_leave_uniform(qpsk_tx_ctx* c, hipStream_t s) {
+    if (!c->uniform) return QPSK_OK;
+    HCHECK(c->d_index.reserve((size_t)c->nch));
+    if (!c->d_rows) {
+        constexpr long n = (long)kCarrierRows * kTxPacket;
+        HCHECK(c->d_rows.reserve((size_t)n));
+        HCHECK(c->h_rows.reserve(2 * (size_t)n));
+        qpsk_tx_phase_table(c->h_rows, n);
+        HCHECK(hipMemcpyAsync(c->d_rows, c->h_rows, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    hipLaunchKernelGGL(tx_seed_kernel, chan_grid(c->nch), dim3(kThreads), 0, s, c->d_index.get(), c->nch,
+                       c->packets);
+    HCHECK(hipGetLastError());
+    c->uniform = false;
+    return QPSK_OK;
+}
+
+// A call of a general context: the plan pre-pass, then the modulator over it.
+static int tx_general(qpsk_tx_ctx* c, const uint8_t* d_bits, const uint8_t* d_active, int npackets, void* d_out,
+                      long ld, hipStream_t s, int enc) {
+    const int r = tx_leave_uniform(c, s);
+    if (r != QPSK_OK) return r;
+    const size_t nplan = (size_t)c->nch * (size_t)npackets;
+    if (nplan > c->d_plan.cap()) {   // the release waits for the kernels that read the old plan
+        HCHECK(c->d_plan.release());
+        HCHECK(c->d_plan.reserve(nplan));
+    }
+    hipLaunchKernelGGL(tx_plan_kernel, chan_grid(c->nch), dim3(kThreads), 0, s, d_bits, d_active,
+                       c->d_state.get(), c->d_index.get(), c->d_plan.get(), c->nch, npackets);
+    HCHECK(hipGetLastError());
+    const long N = (long)npackets * ((long)kTxPacket + c->gap);
+    const long ntile = (N + (kChunk - 1) + kTile - 1) / kTile;
+    const unsigned gx = (unsigned)(kClasses * (((long)c->nch + kClasses * kLoop - 1) / (kClasses * kLoop)));
+    for (long t0 = 0; t0 < ntile; t0 += 65535) {
+        const dim3 grid(gx, (unsigned)lmin(65535L, ntile - t0)), block(kThreads);
+        const uint32_t* plan = c->d_plan.get();
+        const float2* rows = c->d_rows.get();
+        qfmt::with_encoding(enc, [&](auto e) {
+            using E = std::conditional_t<e() == QPSK_OUT_S16, int16_t, uint8_t>;
+            hipLaunchKernelGGL((tx_mask_kernel<e(), E>), grid, block, 0, s, d_bits, plan, rows,
+                               static_cast<E*>(d_out), ld, c->nch, npackets, c->gap, t0);
+        });
+        HCHECK(hipGetLastError());
+    }
+    HCHECK(hipEventRecord(c->ev_last, s));
+    c->packets += (uint64_t)npackets;
+    return QPSK_OK;
+}
+
+// A call of a uniform context: the carrier of the call's samples from the
+// host, tx_batch_kernel, and tx_state_kernel for the next call's history.
+static int tx_uniform(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets, void* d_out, long ld, hipStream_t s,
+                      int enc) {
     const long ntx = (long)npackets * kTxPacket;
     if ((size_t)ntx > c->d_tab.cap()) {   // the release waits for the kernels that read the old table
         HCHECK(c->d_tab.release());
@@ -459,12 +768,130 @@ extern "C" int qpsk_tx_batch_device_enc(qpsk_tx_ctx* c, const uint8_t* d_bits, i
     return QPSK_OK;
 }
 
+// qpsk_tx_batch_masked_device with the element the store pass writes named:
+// d_out is int16 [nch][ld] for QPSK_OUT_S16 and uint8 [nch][ld] G.711 codes for
+// QPSK_OUT_ALAW / QPSK_OUT_ULAW (qpsk_tx_internal.h).  A NULL mask on a uniform
+// context is the plain call and keeps the context uniform.
+extern "C" int qpsk_tx_batch_masked_device_enc(qpsk_tx_ctx* c, const uint8_t* d_bits, const uint8_t* d_active,
+                                               int npackets, void* d_out, long ld, void* stream, int enc) {
+    if (enc != QPSK_OUT_S16 && enc != QPSK_OUT_ALAW && enc != QPSK_OUT_ULAW) return QPSK_EINVAL;
+    const int chk = tx_check(c, d_bits, npackets, d_out, ld);
+    if (chk != QPSK_OK || npackets == 0) return chk;
+    HCHECK(hipSetDevice(c->device));
+    if (c->uniform && !d_active) return tx_uniform(c, d_bits, npackets, d_out, ld, (hipStream_t)stream, enc);
+    return enomem(tx_general(c, d_bits, d_active, npackets, d_out, ld, (hipStream_t)stream, enc));
+}
+
+extern "C" int qpsk_tx_batch_device_enc(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets, void* d_out,
+                                        long ld, void* stream, int enc) {
+    return qpsk_tx_batch_masked_device_enc(c, d_bits, nullptr, npackets, d_out, ld, stream, enc);
+}
+
 extern "C" int qpsk_tx_batch_device(qpsk_tx_ctx* c, const uint8_t* d_bits, int npackets,
                                     int16_t* d_out, long ld, void* stream) {
-    return qpsk_tx_batch_device_enc(c, d_bits, npackets, d_out, ld, stream, QPSK_OUT_S16);
+    return qpsk_tx_batch_masked_device_enc(c, d_bits, nullptr, npackets, d_out, ld, stream, QPSK_OUT_S16);
+}
+
+extern "C" int qpsk_tx_batch_masked_device(qpsk_tx_ctx* c, const uint8_t* d_bits, const uint8_t* d_active,
+                                           int npackets, int16_t* d_out, long ld, void* stream) {
+    return qpsk_tx_batch_masked_device_enc(c, d_bits, d_active, npackets, d_out, ld, stream, QPSK_OUT_S16);
+}
+
+// ---------------------------------------------------------------- channels on their own
+static int range_check(const qpsk_tx_ctx* c, int c0, int n) {
+    return c && c0 >= 0 && n >= 0 && c0 <= c->nch && n <= c->nch - c0 ? QPSK_OK : QPSK_EINVAL;
+}
+
+extern "C" int qpsk_tx_reset_channels(qpsk_tx_ctx* c, int c0, int n) {
+    if (range_check(c, c0, n) != QPSK_OK) return QPSK_EINVAL;
+    int r = qpsk_tx_sync(c);
+    if (r != QPSK_OK || n == 0) return r;
+    r = tx_leave_uniform(c, c->stream);
+    if (r != QPSK_OK) return enomem(r);
+    HCHECK(hipMemsetAsync(c->d_index.get() + c0, 0, sizeof(uint64_t) * (size_t)n, c->stream));
+    HCHECK(hipMemsetAsync(c->d_state.get() + c0, 0, sizeof(uint32_t) * (size_t)n, c->stream));
+    HCHECK(hipStreamSynchronize(c->stream));
+    return QPSK_OK;
+}
+
+// own indices and canonical state words of [c0, c0 + n) after the calls in flight
+static int tx_read_state(qpsk_tx_ctx* c, int c0, int n, uint64_t* idx, uint32_t* words) {
+    const int r = qpsk_tx_sync(c);
+    if (r != QPSK_OK) return r;
+    if (c->uniform) {
+        for (int i = 0; i < n; i++) idx[i] = c->packets;
+    } else {
+        HCHECK(hipMemcpy(idx, c->d_index.get() + c0, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
+    }
+    if (!words) return QPSK_OK;
+    HCHECK(hipMemcpy(words, c->d_state.get() + c0, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) words[i] = idx[i] ? words[i] & kDibits : 0u;   // not read before a first packet
+    return QPSK_OK;
+}
+
+extern "C" int qpsk_tx_channel_packets(qpsk_tx_ctx* c, int c0, int n, uint64_t* out) {
+    if (range_check(c, c0, n) != QPSK_OK || (n > 0 && !out)) return QPSK_EINVAL;
+    if (n == 0) return qpsk_tx_sync(c);
+    return tx_read_state(c, c0, n, out, nullptr);
+}
+
+namespace {
+constexpr uint32_t kSnapMagic = 0x53585451u, kSnapVersion = 1u;   // "QTXS"
+constexpr size_t kSnapHeader = 16;
+}  // namespace
+
+extern "C" size_t qpsk_tx_state_size(int n) { return n < 1 ? 0 : kSnapHeader + 12 * (size_t)n; }
+
+extern "C" int qpsk_tx_state_save(qpsk_tx_ctx* c, int c0, int n, void* buf, size_t size) {
+    if (range_check(c, c0, n) != QPSK_OK || n < 1 || !buf || size < qpsk_tx_state_size(n)) return QPSK_EINVAL;
+    uint64_t* idx = (uint64_t*)malloc(12 * (size_t)n);
+    if (!idx) return QPSK_ENOMEM;
+    uint32_t* words = (uint32_t*)(idx + n);
+    const int r = tx_read_state(c, c0, n, idx, words);
+    if (r == QPSK_OK) {
+        const uint32_t head[4] = {kSnapMagic, kSnapVersion, (uint32_t)n, 0u};
+        memcpy(buf, head, kSnapHeader);
+        memcpy((char*)buf + kSnapHeader, idx, 12 * (size_t)n);   // the indices, then the words
+    }
+    free(idx);
+    return r;
+}
+
+extern "C" int qpsk_tx_state_load(qpsk_tx_ctx* c, int c0, int n, const void* buf, size_t size) {
+    if (range_check(c, c0, n) != QPSK_OK || n < 1 || !buf || size < qpsk_tx_state_size(n)) return QPSK_EINVAL;
+    uint32_t head[4];
+    memcpy(head, buf, kSnapHeader);
+    if (head[0] != kSnapMagic || head[1] != kSnapVersion || head[2] != (uint32_t)n || head[3] != 0u)
+        return QPSK_EINVAL;
+    uint64_t* idx = (uint64_t*)malloc(12 * (size_t)n);
+    if (!idx) return QPSK_ENOMEM;
+    uint32_t* words = (uint32_t*)(idx + n);
+    memcpy(idx, (const char*)buf + kSnapHeader, 12 * (size_t)n);
+    int r = QPSK_OK;
+    for (int i = 0; i < n; i++)
+        if ((words[i] & ~kDibits) || (!idx[i] && words[i])) r = QPSK_EINVAL;
+    if (r == QPSK_OK) r = qpsk_tx_sync(c);
+    if (r == QPSK_OK) {
+        r = enomem(tx_leave_uniform(c, c->stream));
+        if (r == QPSK_OK)
+            r = herr(hipMemcpyAsync(c->d_index.get() + c0, idx, sizeof(uint64_t) * (size_t)n,
+                                    hipMemcpyHostToDevice, c->stream));
+        if (r == QPSK_OK)
+            r = herr(hipMemcpyAsync(c->d_state.get() + c0, words, sizeof(uint32_t) * (size_t)n,
+                                    hipMemcpyHostToDevice, c->stream));
+        const int r2 = herr(hipStreamSynchronize(c->stream));   // idx is freed below
+        if (r == QPSK_OK) r = r2;
+    }
+    free(idx);
+    return r;
 }
 
 extern "C" int qpsk_tx_batch(qpsk_tx_ctx* c, const uint8_t* bits, int npackets, int16_t* out, long ld) {
+    return qpsk_tx_batch_masked(c, bits, nullptr, npackets, out, ld);
+}
+
+extern "C" int qpsk_tx_batch_masked(qpsk_tx_ctx* c, const uint8_t* bits, const uint8_t* active, int npackets,
+                                    int16_t* out, long ld) {
     const int chk = tx_check(c, bits, npackets, out, ld);
     if (chk != QPSK_OK || npackets == 0) return chk;
     HCHECK(hipSetDevice(c->device));
@@ -474,12 +901,15 @@ extern "C" int qpsk_tx_batch(qpsk_tx_ctx* c, const uint8_t* bits, int npackets, 
     HCHECK(hipEventSynchronize(c->ev_last));
     const size_t nbits = (size_t)c->nch * (size_t)npackets * kPacketBits;
     const size_t N = (size_t)npackets * (size_t)(kTxPacket + (long)c->gap);
-    qhip::DevBuf<uint8_t> d_bits;   // released on return, after the synchronisation
+    const size_t nact = active ? (size_t)c->nch * (size_t)npackets : 0;
+    qhip::DevBuf<uint8_t> d_bits, d_active;   // released on return, after the synchronisation
     qhip::DevBuf<int16_t> d_out;
     int r = herr(d_bits.reserve(nbits));
+    if (r == QPSK_OK) r = herr(d_active.reserve(nact));
     if (r == QPSK_OK) r = herr(d_out.reserve(N * (size_t)c->nch));
     if (r == QPSK_OK) r = herr(hipMemcpyAsync(d_bits, bits, nbits, hipMemcpyHostToDevice, c->stream));
-    if (r == QPSK_OK) r = qpsk_tx_batch_device(c, d_bits, npackets, d_out, (long)N, c->stream);
+    if (r == QPSK_OK && active) r = herr(hipMemcpyAsync(d_active, active, nact, hipMemcpyHostToDevice, c->stream));
+    if (r == QPSK_OK) r = qpsk_tx_batch_masked_device(c, d_bits, d_active, npackets, d_out, (long)N, c->stream);
     // only the written samples come back: out[c][N .. ld) keeps its contents
     if (r == QPSK_OK)
         r = herr(hipMemcpy2DAsync(out, sizeof(int16_t) * (size_t)ld, d_out, sizeof(int16_t) * N,

@@ -42,6 +42,10 @@ void *qpsk_tx_host_stream(const struct qpsk_tx_ctx *c);
  * uint8 [nch][ld], any address: the planar G.711 formats without a pre-pass. */
 int qpsk_tx_batch_device_enc(struct qpsk_tx_ctx *c, const uint8_t *d_bits, int npackets, void *d_out,
                              long ld, void *stream, int enc);
+/* the same for qpsk_tx_batch_masked_device(); d_active NULL = every slot
+ * active, which is the call above */
+int qpsk_tx_batch_masked_device_enc(struct qpsk_tx_ctx *c, const uint8_t *d_bits, const uint8_t *d_active,
+                                    int npackets, void *d_out, long ld, void *stream, int enc);
 /* what qpsk_tx_sync() and qpsk_tx_destroy() wait for moves behind the work
  * enqueued on `stream` so far: the conversion that follows the modulator */
 int qpsk_tx_mark(struct qpsk_tx_ctx *c, void *stream);
