@@ -5,128 +5,25 @@ addresses used here; this file runs them and compares the whole destination
 buffer (the guard in front, the rows, the row tails, the guard behind) with
 the host twin sc.tx_batch_host, which tests/test_tx_batch.py pins to the
 oracle and the reference over 2,049 packets.  Exact equality everywhere; a
-failure names the tile of the first wrong element and its class.  Run with
+failure names the tile of the first wrong element and its class.  The block,
+the calls and the comparison are tests/tx_sweep_run.py's, shared with the
+sweep of the general context (tests/test_gpu_tx_mask_sweep.py).  Run with
 -m gpu."""
 import numpy as np
 import pytest
 
 import singlecarrier_amd as sc
 import tx_geometry as g
-from g711 import CODES, compress
+import tx_sweep_run as run
 from tx_geometry import CASES
+from tx_sweep_run import FMT, Block, expected, payload, send
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-GUARD = 64                                  # sentinel elements in front of and behind the block
-SENT = {2: 0x5A5A, 1: 0xC3}
-FMT = {"s16": sc.OUT_S16, "alaw": sc.OUT_ALAW, "ulaw": sc.OUT_ULAW}
-
-
-def payload(case, seed):
-    return np.random.default_rng(seed).integers(0, 2, (case.nch, case.npk, 8, 62), dtype=np.uint8)
-
-
-def expected(case, bits, enc):
-    """the host twin's samples [nch][n] as elements of the encoding"""
-    host = sc.tx_batch_host(bits, gap=case.gap)
-    assert host.shape == (case.nch, case.n)
-    if enc == sc.OUT_S16:
-        return host
-    if case.gap < 100_000:
-        return compress(host, enc)
-    # nearly all gap: the code of 0 everywhere, the packets compressed one by one
-    pk = host.reshape(case.nch, case.npk, case.P)
-    assert not pk[:, :, g.TX_PACKET:].any()
-    want = np.full(pk.shape, CODES[enc][32768], np.uint8)
-    want[:, :, :g.TX_PACKET] = compress(pk[:, :, :g.TX_PACKET], enc)
-    return want.reshape(case.nch, case.n)
-
-
-class Block:
-    """A case's destination inside a sentinel-filled device buffer, row 0 at
-    case.addr16 bytes past a 16-byte boundary, and the host image of what the
-    buffer is to hold."""
-
-    def __init__(self, case):
-        self.case, es = case, case.es
-        self.dtype = torch.int16 if es == 2 else torch.uint8
-        body = self.body = (case.nch - 1) * case.ld + case.n
-        self.full = torch.full((GUARD + 16 + body + GUARD,), SENT[es], dtype=self.dtype, device="cuda")
-        self.start = GUARD + ((case.addr16 - self.full.data_ptr() - GUARD * es) % 16) // es
-        flat = self.full[self.start:self.start + body]
-        self.rows = torch.as_strided(flat, (case.nch, case.n), (case.ld, 1), flat.storage_offset())
-        # the addresses the CPU coverage test assumed
-        assert self.rows.data_ptr() % 16 == case.addr16
-        for c in (0, case.nch - 1):
-            assert (self.rows[c].data_ptr() // es) % 8 == g.alignment(case.addr16, es, c, case.ld)
-        self.image = np.full(self.full.numel(), SENT[es], np.int16 if es == 2 else np.uint8)
-
-    def expect(self, want, first=0, last=None):
-        """packets [first, last) of want [nch][n] into the image"""
-        case = self.case
-        lo, hi = first * case.P, (case.npk if last is None else last) * case.P
-        for c in range(case.nch):
-            s = self.start + c * case.ld
-            self.image[s + lo:s + hi] = want[c, lo:hi]
-
-    def clear(self):
-        self.full.fill_(SENT[self.case.es])
-        self.image[...] = SENT[self.case.es]
-
-    def where(self, i):
-        case = self.case
-        e = i - self.start
-        if e < 0:
-            return f"{-e} elements in front of the block"
-        c, p = divmod(e, case.ld)
-        if c >= case.nch or (c == case.nch - 1 and p >= case.n):
-            return f"{e - (case.nch - 1) * case.ld - case.n} elements behind the block"
-        if p >= case.n:
-            return f"channel {c}'s row tail, {p - case.n} elements behind its row"
-        return case.locate(c, p)
-
-    def check(self, what):
-        torch.cuda.synchronize()
-        got = self.full.cpu().numpy()
-        bad = np.flatnonzero(got != self.image)
-        if bad.size:
-            i = int(bad[0])
-            raise AssertionError(f"{what}: {bad.size} elements differ; the first, {int(got[i])} for {int(self.image[i])}, "
-                                 f"at {self.where(i)}; the last at {self.where(int(bad[-1]))}")
-        return got
-
-
-def send(tx, case, block, d_bits, enc, calls=None, first=0):
-    """the case's packets from `first` on in calls of `calls` packets, each at
-    out + k * P"""
-    k = first
-    for n in (case.calls if calls is None else calls):
-        part = d_bits[:, k:k + n].contiguous()
-        out = block.rows[:, k * case.P:]
-        if enc == sc.OUT_S16:
-            tx.modulate_device(part, out)
-        else:
-            tx.modulate_device_fmt(part, out, enc | sc.OUT_PLANAR)
-        k += n
-    return k
-
 
 def run_case(name, enc, seed):
-    case = CASES[name]
-    assert case.es == (2 if enc == sc.OUT_S16 else 1)
-    bits = payload(case, seed)
-    want = expected(case, bits, enc)
-    block = Block(case)
-    tx = sc.Transmitter(case.nch, gap=case.gap)
-    try:
-        assert send(tx, case, block, torch.from_numpy(bits).cuda(), enc) == case.npk
-        tx.sync()
-        assert tx.packets() == case.npk
-        block.expect(want)
-        block.check(name)
-    finally:
-        tx.close()
+    run.run_case(name, CASES[name], enc, seed)
 
 
 # ------------------------------------------------------------------ every cut
@@ -222,43 +119,7 @@ def test_row_offsets_past_2_to_32_bytes(name):
     """3 rows 2^31 + 1 int16 (2^32 + 1 codes) apart: row 1 starts past 4 GiB
     and row 2 past 8 GiB of the block.  The buffer is not filled: sentinels
     lie only around the three rows, each compared with its guards."""
-    case = CASES[name]
-    enc, es = FMT[name.split("_")[1]], case.es
-    count = GUARD + 16 + (case.nch - 1) * case.ld + case.n + GUARD
-    if torch.cuda.mem_get_info()[0] < count * es + 6 * 2**30:
-        pytest.skip(f"needs about {count * es / 1e9:.0f} GB of device memory")
-    bits = payload(case, 6)
-    want = expected(case, bits, enc)
-    full = flat = rows = tx = None
-    try:
-        full = torch.empty(count, dtype=torch.int16 if es == 2 else torch.uint8, device="cuda")
-        start = GUARD + ((case.addr16 - full.data_ptr() - GUARD * es) % 16) // es
-        for c in range(case.nch):
-            full[start + c * case.ld - GUARD:start + c * case.ld + case.n + GUARD] = SENT[es]
-        flat = full[start:start + (case.nch - 1) * case.ld + case.n]
-        rows = torch.as_strided(flat, (case.nch, case.n), (case.ld, 1), flat.storage_offset())
-        assert rows.data_ptr() % 16 == case.addr16
-        assert rows[1].data_ptr() - rows[0].data_ptr() > 2**32 and rows[2].data_ptr() - rows[0].data_ptr() > 2**33
-        tx = sc.Transmitter(case.nch, gap=case.gap)
-        d_bits = torch.from_numpy(bits).cuda()
-        if enc == sc.OUT_S16:
-            tx.modulate_device(d_bits, rows)
-        else:
-            tx.modulate_device_fmt(d_bits, rows, enc | sc.OUT_PLANAR)
-        tx.sync()
-        for c in range(case.nch):
-            got = full[start + c * case.ld - GUARD:start + c * case.ld + case.n + GUARD].cpu().numpy()
-            image = np.full(got.size, SENT[es], got.dtype)
-            image[GUARD:GUARD + case.n] = want[c]
-            bad = np.flatnonzero(got != image)
-            assert bad.size == 0, (f"{name}: row {c}, {bad.size} elements differ, the first at "
-                                   + (case.locate(c, int(bad[0]) - GUARD) if GUARD <= bad[0] < GUARD + case.n
-                                      else f"guard element {int(bad[0]) - GUARD}"))
-    finally:
-        if tx is not None:
-            tx.close()
-        del full, flat, rows
-        torch.cuda.empty_cache()
+    run.run_rows4g(name, CASES[name], FMT[name.split("_")[1]], 6)
 
 
 @pytest.mark.parametrize("nch", g.GRID_X_NCH)

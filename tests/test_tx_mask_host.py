@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import singlecarrier_amd as sc
+import tx_mask_geometry as mg
 from tx_geometry import golden_payload
 from tx_mask_cases import HEADER, PACKET, Restated, Twin, masks, payload, snapshot
 
@@ -51,6 +52,40 @@ def test_masked_host_against_the_restatement(gap):
         g = got.reshape(nch, npk, PACKET + gap)
         assert not g[m == 0].any() and not g[:, :, PACKET:].any()
         assert g[m != 0][:, :PACKET].any(axis=1).all()
+    np.testing.assert_array_equal(twin.st, rest.st)
+
+
+@pytest.mark.parametrize("gap", [903, 0])
+@pytest.mark.parametrize("kind", ["sweep", "joins"])
+def test_masked_host_against_the_restatement_on_the_sweep_masks(kind, gap):
+    """The masks of tests/test_gpu_tx_mask_sweep.py, where the twin is the
+    yardstick, cut down to two calls of their first slots: 136 channels x 40
+    slots of the de Bruijn mask hold every 4-slot window in every channel, and
+    the first 80 slots of the join mask several channels' first packets, later
+    than slot 0, while others stay idle throughout.  The second call starts
+    from the state the first left, in the sweep mask behind idle tails of up
+    to 4 slots."""
+    if kind == "sweep":
+        nch, npk = mg.SWEEP_NCH, 40
+        mask = mg.sweep_mask(nch, 2 * npk, 300 + gap)
+        win = mg.windows(mask[:, :npk])[:, 1:npk - 2]
+        assert all(set(row.tolist()) == set(range(16)) for row in win)
+        tails = npk - 1 - np.array([np.flatnonzero(r)[-1] for r in mask[:, :npk]])
+        assert (tails > 0).sum() >= 8 and tails.max() == 4    # B's longest run of zeros
+    else:
+        npk = 80
+        mask = mg.join_case(gap).mask[:, :2 * npk]
+        nch = mask.shape[0]
+        first = np.array([np.flatnonzero(r)[0] if r.any() else -1 for r in mask])
+        assert ((0 < first) & (first < npk)).sum() >= 3 and (first >= npk).sum() >= 3
+        assert (first < 0).sum() >= 3                         # and channels that do not join in these slots
+    twin, rest = Twin(nch), Restated(nch)
+    for call in range(2):
+        bits, m = payload(310 + call, nch, npk), mask[:, npk * call:npk * call + npk]
+        got = twin.call(bits, gap, m)
+        np.testing.assert_array_equal(got, rest.call(bits, gap, m != 0))
+        g = got.reshape(nch, npk, PACKET + gap)
+        assert not g[m == 0].any() and g[m != 0][:, :PACKET].any(axis=1).all()
     np.testing.assert_array_equal(twin.st, rest.st)
 
 
