@@ -118,6 +118,23 @@ def _frames(x):
     return x
 
 
+class Chan(C.Structure):
+    """qc_chan_t (oracle/cpu_ref.h): one channel's carried state."""
+    _fields_ = [("rx_timing", C.c_int32), ("frame", C.c_uint32), ("mode", C.c_int32),
+                ("dprev", C.c_float * 2 * 290), ("hist", C.c_int16 * 1880 * 2)]
+
+
+def chan_lib():
+    """cpu_lib() with the one-frame step declared: qc_chan_init_mode(ch, mode) and
+    qc_rx_frame(ch, in, bits, trace) -> valid."""
+    lib = cpu_lib()
+    lib.qc_chan_init_mode.argtypes = [C.c_void_p, C.c_int]
+    lib.qc_chan_init_mode.restype = None
+    lib.qc_rx_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.qc_rx_frame.restype = C.c_int
+    return lib
+
+
 def cpu_rx(x, threads: int = 0, trace: bool = False, mode: int = MODE_REF):
     """Restatement over x [nch][nframes][1880] (or [nframes][1880]).
     Returns bits [nch][nframes][62] u8, valid [nch][nframes] u8, trace|None."""

@@ -82,21 +82,11 @@ def test_reference_is_even_in_its_input(mode, name):
 
 
 # ------------------------------------------------------- B. offset invariance
-class _Chan(C.Structure):
-    """qc_chan_t (oracle/cpu_ref.h)."""
-    _fields_ = [("rx_timing", C.c_int32), ("frame", C.c_uint32), ("mode", C.c_int32),
-                ("dprev", C.c_float * 2 * 290), ("hist", C.c_int16 * 1880 * 2)]
-
-
 def _run_from(x, mode, frame):
     """One channel x [nframes][1880] through qc_rx_frame with ch->frame preset;
     (bits, trace) per frame."""
-    lib = oracle.cpu_lib()
-    lib.qc_chan_init_mode.argtypes = [C.c_void_p, C.c_int]
-    lib.qc_chan_init_mode.restype = None
-    lib.qc_rx_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.qc_rx_frame.restype = C.c_int
-    ch = _Chan()
+    lib = oracle.chan_lib()
+    ch = oracle.Chan()
     lib.qc_chan_init_mode(C.byref(ch), mode)
     assert ch.frame == 0 and ch.rx_timing == 3 and ch.mode == mode, "qc_chan_t layout changed"
     ch.frame = frame

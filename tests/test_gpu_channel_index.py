@@ -18,10 +18,10 @@ import pytest
 import oracle
 import rxcheck
 import singlecarrier_amd as sc
+from traffic import at_frame as _at_frame, frame_of as _frame_of, keywords as _keywords
 
 pytestmark = pytest.mark.gpu
 
-KS_FRAMES = 1057
 MODES = [sc.MODE_REFERENCE, sc.MODE_DEC752]
 MODE_IDS = ["reference", "dec752"]
 
@@ -110,22 +110,6 @@ def test_tiny_calls_reset_one_channel(F, mode):
 
 
 # ---------------------------------------------------------- C. keystream wrap
-def _frame_of(snap):
-    return int(np.frombuffer(snap[24:32], "<u8")[0])
-
-
-def _at_frame(snap, old, G):
-    """tests/test_gpu_frame_index.py's header edit: StateHdr.frame from `old` to G."""
-    assert snap[:8] == b"QPSKSTA1" and len(snap) >= 64 and _frame_of(snap) == old, "StateHdr layout changed"
-    return snap[:24] + np.array([G], "<u8").tobytes() + snap[32:]
-
-
-def _keywords(first, nf):
-    ks = oracle.keystream(32767)
-    idx = (62 * ((first + np.arange(nf)) % KS_FRAMES)[:, None] + np.arange(62)[None, :]) % 32767
-    return ks[idx]
-
-
 def test_keystream_wraps_inside_a_call():
     """A context at index 1055 (a fresh snapshot with an edited header), 64
     channels joined at own indices 0, 1, 1056, 2113 and 2^32 + 5 after two real
